@@ -7,9 +7,14 @@ configs[1], k* = 2.3).  `--streams` GOP pipelines are in flight per GPU, EACH WI
 resident input: the mask kernel reads HBM, not the Infinity Cache).  `--gops-per-call G` makes a step ONE rbf_encode_runs call over G GOPs
 (one launch sequence per G x 29 inter-frames); the default stays 1 and the default run adds a `batched_gops` leg with 4.
 
-Timing protocol: --warmup steps, then untimed settling (windows of --steps steps until two agree within 2 % and 30 ms have gone by),
-then NINE regions of EXACTLY --steps steps, each between barrier + synchronize, max over ranks; the MEDIAN region is the headline
-(`steps` = --steps, `regions_ms` lists all nine).  One long region follows as `steady_state`.
+A plain run (`--gpus 1 --steps N --warmup W`) does only what its headline needs: set-up, W warm-up steps, then ONE region of exactly N
+steps between barrier + synchronize (max over ranks) -- `value` and `ms_per_step` are that region's -- and the line.  `--dump-outputs DIR`
+then writes what the last timed step computed (dump_outputs).  The protocol below, and everything measured or checked after it (per-kernel
+timing, steady state, roofline, PCIe figures, the oracle check, the CPU baseline, the legs and the clip legs), runs with `--full` only.
+
+Timing protocol of `--full`: --warmup steps, then untimed settling (windows of --steps steps until two agree within 2 % and 30 ms have
+gone by), then NINE regions of EXACTLY --steps steps, each between barrier + synchronize, max over ranks; the MEDIAN region is the
+headline (`steps` = --steps, `regions_ms` lists all nine).  One long region follows as `steady_state`.
 
 With N > 1 every rank encodes its own GOPs (weak scaling), compacts each step's rows into one exact-size record on the device and
 gathers it to rank 0 over RCCL inside the step.  `python bench.py --gpus N` without a launcher environment starts the N ranks ITSELF (one
@@ -92,6 +97,9 @@ def parse_args():
     ap.add_argument("--no-shard-proxy", action="store_true", help="skip the shard_proxy leg (one rank's share of configs 3 / 5 at N = 2, 4, 8, timed on this GPU)")
     ap.add_argument("--ballast", type=int, default=0, help="diagnostic: allocate a dummy device block of random size (this seed) in front of every pipeline's first step, so that the contexts' scratch lands elsewhere in HBM (profiles/r06_placement.txt)")
     ap.add_argument("--clip-block-gops", type=int, default=0, help="clip mode: keyframe intervals a rank hands to the GPU in ONE rbf_encode_runs launch sequence; 0 = auto (one block per pipeline and pass, see clip_blocks), 1 = one call per run of inter-frames (round 4)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: settling and the median of nine regions, per-kernel timing, steady state, roofline, "
+                    "PCIe figures, the oracle check, the CPU baseline, the legs and the clip legs.  Without it a run times exactly --steps steps after --warmup and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -302,6 +310,8 @@ def main():
         return spawn_ranks(args)
     install_term_handler()
     try:
+        if args.clip_frames and args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the GOP pipelines' last step; the clip mode (--clip-frames) has no such step")
         return clip_main(args) if args.clip_frames else bench_main(args)
     except SystemExit as e:
         if e.code in (0, None):
@@ -357,14 +367,18 @@ def bench_main(args):
     coder = coders[0]
     density = args.density or P_KSTAR_2_3
     host_gops = []                                # [pipeline][resident gop] -> (F, H, W, 3) host frames
-    for k in range(ncoders):
-        if k and args.shared_gop:
-            host_gops.append(host_gops[0])
-            continue
-        host_gops.append([np.concatenate([np.stack(make_gop(1000 * 2 + 64 * rank + k + 16 * g + 4096 * j, W, H, F, p=density, dtype=dtype)) for j in range(GPC)])
-                          for g in range(G_res)])
-        for g in range(G_res):
-            coders[k].load_frames(host_gops[k][g], g)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(16) as pool:          # every GOP is its own seeded stream: the same frames as one thread makes, in a fraction of the set-up time
+        made = {(k, g): pool.submit(lambda k, g: np.concatenate([np.stack(make_gop(1000 * 2 + 64 * rank + k + 16 * g + 4096 * j, W, H, F, p=density, dtype=dtype))
+                                                                  for j in range(GPC)]), k, g)
+                for k in range(1 if args.shared_gop else ncoders) for g in range(G_res)}
+        for k in range(ncoders):
+            if k and args.shared_gop:
+                host_gops.append(host_gops[0])
+                continue
+            host_gops.append([made[(k, g)].result() for g in range(G_res)])
+            for g in range(G_res):
+                coders[k].load_frames(host_gops[k][g], g)
     torch.cuda.synchronize(device)
     per_gop_bytes = host_gops[0][0].nbytes // (3 if planar else 1)
     resident_mb = per_gop_bytes * G_res * (1 if args.shared_gop else ncoders) / 1e6
@@ -509,6 +523,56 @@ def bench_main(args):
             elapsed = float(te.item())
         return elapsed, kt
 
+    pixels_per_step = coded_pairs * n * world
+    config = {"workload": "%dx%d YUV444 %d-bit synthetic %d-frame GOP%s (%d inter-frames/step/GPU), %s, threshold 0, %s"
+                          % (W, H, args.bits, F, "" if GPC == 1 else " x %d GOPs batched into ONE launch sequence per step (rbf_encode_runs)" % GPC, coded_pairs,
+                             "p=%g" % args.density if args.density else "k*=2.3",
+                             "planar Y resident (the mask stage reads luma only)" if planar else "interleaved YUV444 resident"),
+              "gops_per_call": GPC,
+              "layout": "planar Y" if planar else "interleaved", "resident_gops_per_pipeline": G_res,
+              "inputs": "resident in HBM before the timed region: %s; the timed step starts at the mask kernel"
+                        % ("Y planes extracted from the YUV444 frames on the host and uploaded once (the `interleaved_yuv444` leg keeps whole frames resident instead)" if planar else "whole interleaved YUV444 frames, uploaded once"),
+              "pixels_per_step": pixels_per_step, "gather_to_rank0": bool(gather), "gop_pipelines_per_gpu": ncoders,
+              "distinct_gop_per_pipeline": not args.shared_gop, "resident_input_mb_per_gpu": round(resident_mb, 1),
+              "gather": "exact-size: all_gather of the used sizes, then one grouped point-to-point message per peer; rank 0's own records are not sent" if gather else None,
+              "steps_per_gather": G if gather else 0,
+              "lds_tile_kib": args.lds_tile_kib or "auto", "generic_kernels": bool(args.generic_kernels),
+              "hash_table": "k_hash_table runs in every step (--rebuild-hash-table)" if args.rebuild_hash_table else
+                            "one pixel-index hash table per (device, frame size, seeds), shared by the pipelines' contexts; built once, before the timed region" if args.streams > 1 else
+                            "built once; rewritten in every step by the query kernel (sole holder: keeps the table in the Infinity Cache for the next insert)",
+              "stages": "residual mask -> host params -> insert -> query+witness",
+              "launcher": os.environ.get("RBF_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "single process"),
+              "rccl_ranks": world if (use_dist and args.backend == "nccl") else 0, "backend": args.backend if use_dist else None,
+              "ranks_share_one_device": bool(args.one_device),
+              "multi_gpu_note": "N>1 on one node was never measured by the builder (1-GPU boxes only); what exists: every rank's share of the N = 2 / 4 / 8 split timed on ONE GPU (the `shard_proxy` leg: a prediction, gather stubbed), world-2 / world-8 runs of the real kernels on ONE device over gloo (tests/test_gpu_dist_shared.py), gloo world-2/3 CPU tests (incl. the self-spawn launcher, a rank killed mid-gather, the failure line) and RCCL world-1 tests"}
+
+    def headline(elapsed):
+        """The contract's keys of the line, from a region of exactly --steps steps that took `elapsed` seconds."""
+        return {"metric": METRIC, "value": round(pixels_per_step * args.steps / elapsed / 1e6, 2), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "u64", "data": "synthetic"}
+
+    def dump_last_step():
+        # step s ran on pipeline s % ncoders (either feed, see run_steps) and nothing has run on that pipeline since
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, coders[(state["s"] - 1) % ncoders].results(), n)
+
+    if not args.full:
+        set_phase("timed")
+        elapsed, _ = timed(args.steps, False)
+        dump_last_step()
+        out = headline(elapsed)
+        out.update({"headline_region": "one region of exactly %d steps after %d warm-up steps" % (args.steps, args.warmup), "config": config})
+        if og is not None:
+            og.close()
+        set_phase("shutdown")
+        if use_dist:
+            bounded_barrier(dist, device, "final barrier")
+            dist.destroy_process_group()
+        if rank == 0:
+            print_line(out)
+        return
+
     # Settling (untimed, after the --warmup steps the caller asked for): the first regions after start-up run 8-10 % slower than the
     # steady state (clocks, caches, the pipelines' queues), so windows of --steps steps are run until two consecutive ones agree within
     # 2 % -- or 30 ms have gone by.  What is then timed is what a warm service does.
@@ -535,7 +599,9 @@ def bench_main(args):
     # (>= MIN_REGION_S) follows as `steady_state`: what the pipelines sustain without the fill and drain of a short region.
     REGIONS = 1 if args.exact_steps else 9
     set_phase("timed")
+    state["s"] = 0                                # (the pipelines are drained: the regions' steps, and so their last one, no longer depend on how long settling took)
     regions = [timed(args.steps, False) for _ in range(REGIONS)]      # (no HIP events inside the headline's regions)
+    dump_last_step()
     order = sorted(range(REGIONS), key=lambda i: regions[i][0])
     elapsed = regions[order[REGIONS // 2]][0]
     host_region = host_s.get("region", 0.0)
@@ -580,14 +646,10 @@ def bench_main(args):
             checked.append((host_gops[k][g], coders[k].results()))
     res_all = [rows for _, rows in checked]
     res = res_all[0]
-    pixels_per_step = coded_pairs * n * world
     value = pixels_per_step * steps_timed / elapsed / 1e6
 
-    out = {
-        "metric": METRIC,
-        "value": round(value, 2), "unit": "Mpixel/s", "n_gpus": world, "steps": steps_timed, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / steps_timed * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+    out = headline(elapsed)
+    out.update({
         "requested_steps": args.steps, "steps_timed": steps_timed, "timed_region_ms": round(elapsed * 1e3, 2),
         "regions_ms": [round(r[0] * 1e3, 3) for r in regions], "headline_region": "median of %d regions of exactly %d steps" % (REGIONS, args.steps),
         "settle": settle, "steady_state": steady,
@@ -595,28 +657,8 @@ def bench_main(args):
         "host_feed": ("one thread per pipeline, each calling rbf_encode_gop on its own context" if (args.host_threads and not gather and ncoders > 1) else
                       "one thread: rbf_encode_gop_begin of step s+%d is enqueued before rbf_encode_gop_finish of step s" % ahead if ahead else
                       "one thread, one blocking rbf_encode_gop per step"),
-        "config": {"workload": "%dx%d YUV444 %d-bit synthetic %d-frame GOP%s (%d inter-frames/step/GPU), %s, threshold 0, %s"
-                               % (W, H, args.bits, F, "" if GPC == 1 else " x %d GOPs batched into ONE launch sequence per step (rbf_encode_runs)" % GPC, coded_pairs,
-                                  "p=%g" % args.density if args.density else "k*=2.3",
-                                  "planar Y resident (the mask stage reads luma only)" if planar else "interleaved YUV444 resident"),
-                   "gops_per_call": GPC,
-                   "layout": "planar Y" if planar else "interleaved", "resident_gops_per_pipeline": G_res,
-                   "inputs": "resident in HBM before the timed region: %s; the timed step starts at the mask kernel"
-                             % ("Y planes extracted from the YUV444 frames on the host and uploaded once (the `interleaved_yuv444` leg keeps whole frames resident instead)" if planar else "whole interleaved YUV444 frames, uploaded once"),
-                   "pixels_per_step": pixels_per_step, "gather_to_rank0": bool(gather), "gop_pipelines_per_gpu": ncoders,
-                   "distinct_gop_per_pipeline": not args.shared_gop, "resident_input_mb_per_gpu": round(resident_mb, 1),
-                   "gather": "exact-size: all_gather of the used sizes, then one grouped point-to-point message per peer; rank 0's own records are not sent" if gather else None,
-                   "steps_per_gather": G if gather else 0,
-                   "lds_tile_kib": args.lds_tile_kib or "auto", "generic_kernels": bool(args.generic_kernels),
-                   "hash_table": "k_hash_table runs in every step (--rebuild-hash-table)" if args.rebuild_hash_table else
-                                 "one pixel-index hash table per (device, frame size, seeds), shared by the pipelines' contexts; built once, before the timed region" if args.streams > 1 else
-                                 "built once; rewritten in every step by the query kernel (sole holder: keeps the table in the Infinity Cache for the next insert)",
-                   "stages": "residual mask -> host params -> insert -> query+witness",
-                   "launcher": os.environ.get("RBF_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "single process"),
-                   "rccl_ranks": world if (use_dist and args.backend == "nccl") else 0, "backend": args.backend if use_dist else None,
-                   "ranks_share_one_device": bool(args.one_device),
-                   "multi_gpu_note": "N>1 on one node was never measured by the builder (1-GPU boxes only); what exists: every rank's share of the N = 2 / 4 / 8 split timed on ONE GPU (the `shard_proxy` leg: a prediction, gather stubbed), world-2 / world-8 runs of the real kernels on ONE device over gloo (tests/test_gpu_dist_shared.py), gloo world-2/3 CPU tests (incl. the self-spawn launcher, a rank killed mid-gather, the failure line) and RCCL world-1 tests"},
-    }
+        "config": config,
+    })
     if use_dist:
         # who ran where, and what crossed the links: every rank's device, and the bytes the non-root ranks sent into rank 0 per step
         # (exact-size records: over xGMI on a node, one link per peer)
@@ -1054,6 +1096,34 @@ def pcie_overlapped(torch, device, coder, stream, gops, pixels, reps=24):
     dt = (time.perf_counter() - t0) / reps
     return {"value": round(pixels / dt / 1e6, 1), "ms_per_gop": round(dt * 1e3, 3), "upload_gbps": round(nbytes / dt / 1e9, 1),
             "note": "upload of the next GOP's Y planes on a copy stream under the current GOP's step; one pipeline, pinned host memory"}
+
+
+DUMP_MAX_VALUES = {"mask": 1 << 23, "filter": 3 << 20, "witness": 3 << 20}     # float32 values: 59 MB at most in all; a default 1080p step fits whole
+
+
+def dump_outputs(path, rows, n):
+    """--dump-outputs: the rows a caller of the timed path receives for one step (GopCoder.results()), as DIR/<name>.npy.  Per row
+    (inter-frame pair) in float64: k, l (filter bits), ones (changed pixels), witness_bits, skipped (1 = a pair across a keyframe, not
+    coded).  The bit fields in float32, one value per byte: mask = the packed residual masks, one row per pair; filter / witness = the
+    rows' packed filters / witnesses back to back (row lengths: l, witness_bits); bits past a row's length are cleared.  An array longer
+    than DUMP_MAX_VALUES is a fixed sample: the sorted positions np.random.default_rng(0).choice(size, limit, replace=False)."""
+    os.makedirs(path, exist_ok=True)
+
+    def bits(a, nbits):
+        return np.packbits(np.unpackbits(a)[:nbits]) if nbits else np.zeros(0, np.uint8)
+    arrays = {"k": [r["k"] for r in rows], "l": [r["l"] for r in rows], "ones": [r["ones"] for r in rows],
+              "witness_bits": [r["witness_bits"] for r in rows], "skipped": [1 if r.get("skipped") else 0 for r in rows]}
+    arrays = {name: np.array(v, dtype=np.float64) for name, v in arrays.items()}
+    arrays["mask"] = np.concatenate([bits(r["mask"], n) for r in rows])
+    arrays["filter"] = np.concatenate([bits(r.get("filter", np.zeros(0, np.uint8)), r["l"]) for r in rows])
+    arrays["witness"] = np.concatenate([bits(r.get("witness", np.zeros(0, np.uint8)), r["witness_bits"]) for r in rows])
+    for name, limit in DUMP_MAX_VALUES.items():
+        a = arrays[name]
+        if a.size > limit:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, limit, replace=False))]
+        arrays[name] = a.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _oracle_frame(args):

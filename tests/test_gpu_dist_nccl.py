@@ -96,7 +96,7 @@ def test_rccl_world1_gathers_records_the_gpu_packed():
 
 def test_bench_force_dist_weak_mode():
     os.environ["MASTER_PORT"] = str(38000 + os.getpid() % 2000)
-    res = run([sys.executable, "bench.py", "--force-dist", "--steps", "12", "--warmup", "2", "--width", "640", "--height", "360", "--frames", "8",
+    res = run([sys.executable, "bench.py", "--full", "--force-dist", "--steps", "12", "--warmup", "2", "--width", "640", "--height", "360", "--frames", "8",
                "--gather-every", "4", "--no-cpu-baseline", "--exact-steps", "--clip-leg-frames", "40", "--keyframe-interval", "10", "--clip-steps", "2"], timeout=900)
     assert res["config"]["gather_to_rank0"] and res["verified_vs_oracle"]["frames"] == 7 * 4 * 3 and res["value"] > 0       # 4 pipelines x 3 resident GOPs
     assert res["config"]["gathered_records_parsed_on_rank0"] >= 4 and res["config"]["rccl_ranks"] == 1
@@ -110,7 +110,7 @@ def test_bench_force_dist_weak_mode():
 
 def test_bench_own_launcher_world1():
     """`python bench.py --gpus N` starts its ranks itself: the same launch path at N = 1 (--spawn), RCCL initialised in the child."""
-    res = run([sys.executable, "bench.py", "--spawn", "--force-dist", "--steps", "8", "--warmup", "2", "--width", "640", "--height", "360", "--frames", "6",
+    res = run([sys.executable, "bench.py", "--full", "--spawn", "--force-dist", "--steps", "8", "--warmup", "2", "--width", "640", "--height", "360", "--frames", "6",
                "--gather-every", "4", "--no-cpu-baseline", "--exact-steps", "--no-clips"], timeout=900)
     assert res["config"]["launcher"] == "self-spawned" and res["config"]["rccl_ranks"] == 1 and res["n_gpus"] == 1
     assert res["verified_vs_oracle"]["frames"] == 5 * 4 * 3

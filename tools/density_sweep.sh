@@ -2,7 +2,7 @@
 # SURVEY 8d secondary table: whole-path throughput over the changed-pixel density (1080p, 29 inter-frames per step, four pipelines).
 # Usage (on the GPU box): tools/density_sweep.sh > gpurun_out/density_sweep.txt
 for p in 0.01 0.05 0.08889 0.2 0.3; do
-    python bench.py --density $p --no-cpu-baseline --no-clips --no-legs --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 | python -c "
+    python bench.py --full --density $p --no-cpu-baseline --no-clips --no-legs --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 k = d['kernels_ms_per_step_alone']

@@ -2,7 +2,7 @@
 # Whole-path throughput beyond 1080p: which kernel family (LDS-resident, LDS-tiled, global-memory) the plan
 # picks and what it costs.  Usage (GPU box): tools/large_frames.sh > gpurun_out/large_frames.txt
 run() {
-    timeout 300 python bench.py --no-cpu-baseline --no-clips --no-legs --steps 10 --warmup 2 "$@" 2>/dev/null | grep '^{' | tail -1 | python -c "
+    timeout 300 python bench.py --full --no-cpu-baseline --no-clips --no-legs --steps 10 --warmup 2 "$@" 2>/dev/null | grep '^{' | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 s = d.get('steady_state') or d

@@ -50,7 +50,7 @@ SHAPES = {"g1": ("1920x1080x30_8bit_gpc1", "1920x1080, 30-frame GOP, one GOP per
           "u4": ("1920x1080x30_16bit_gpc4", "1920x1080 16-bit samples, 4 x 30 frames per call")}
 print("# rocprofv3 (%s, tools/%s_profile.sh): kernel time stats and HBM traffic per launch; one MI355X" % (ROUND, ROUND))
 st = stats("default")
-print("\n== default command, four pipelines (python bench.py --steps 20 --warmup 5, without legs / clips / CPU baseline): kernels overlap")
+print("\n== default command, four pipelines (python bench.py --full --steps 20 --warmup 5, without legs / clips / CPU baseline): kernels overlap")
 for k, (calls, avg, pct) in sorted(st.items(), key=lambda kv: -kv[1][2]):
     print("  %-64s calls %6d  avg %10.1f ns  %5.1f%%" % (k, calls, avg, pct))
 traffic = {}

@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r06_profile
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-NL="--no-cpu-baseline --no-verify --no-clips --no-legs"
+NL="--full --no-cpu-baseline --no-verify --no-clips --no-legs"
 SHAPES=${SHAPES:-"g1 g4 c4 u1 u4"}
 if [ -z "${SKIP_DEFAULT:-}" ]; then
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_default" -o stats -- python $ROOT/bench.py $NL --steps 20 --warmup 5 > "$OUT/stats_default.log" 2>&1
