@@ -171,6 +171,21 @@ int rbf_residual_mask_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame
                             uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
                             void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev);
 
+/* ---- A1, all-channel mask ------------------------------------------------------------------- */
+/* rbf_residual_mask_batch with one more argument.  mask_channels = 1: exactly rbf_residual_mask_batch (the luma rule above).
+ * mask_channels >= 2: mask bit = 1 when ANY of the pixel's first mask_channels samples differs between frame f and f+1 -- an exact
+ * comparison of the whole sample, not the int16 rule (a 16-bit change of 0x8000 IS marked).  The reference's inter-frame record is
+ * (mask, every channel of the masked pixels) (improved_video_compressor.py:811-842) and its _apply_frame_diff writes every channel
+ * wherever the mask is 1 (:849-909), so a record built on this mask reconstructs frame f+1 bit for bit even where chroma changed and
+ * luma did not -- the luma mask then has to give up the frame.  Lossless only: RBF_EINVAL (before the stream is touched) for
+ * mask_channels >= 2 with thr_floor != 0, with thr_floors != NULL, or with mask_channels * sample_bytes > pixel_stride_bytes; and for
+ * mask_channels == 0. */
+int rbf_residual_mask_batch_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                               uint32_t nframes, uint32_t width, uint32_t height,
+                               uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
+                               uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
+                               void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev, uint32_t mask_channels);
+
 /* ---- A1, BGR input  (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY), :794-795) --------------------- */
 /* gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15 per pixel -- OpenCV 4.x's integer path for 8- and
  * 16-bit samples; samples 0,1,2 of a pixel are B,G,R (further channels are ignored).  gray_dev receives
@@ -286,6 +301,17 @@ int rbf_encode_runs_begin(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_s
                           void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev,
                           void *filters_dev, uint64_t filter_stride_bytes,
                           void *witnesses_dev, uint64_t witness_stride_bytes, uint64_t *stats_dev);
+/* rbf_encode_runs_begin with the mask rule of rbf_residual_mask_batch_ex (mask_channels: 1 = luma, exactly rbf_encode_runs_begin;
+ * >= 2 = all-channel, same argument checks).  Runs, skipped pairs, counts and filters as rbf_encode_runs_begin; rbf_encode_gop_poll /
+ * rbf_encode_gop_finish complete it. */
+int rbf_encode_runs_begin_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                             uint32_t nframes, uint32_t width, uint32_t height,
+                             uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
+                             uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
+                             const uint8_t *run_starts, const rbf_seeds *seeds,
+                             void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev,
+                             void *filters_dev, uint64_t filter_stride_bytes,
+                             void *witnesses_dev, uint64_t witness_stride_bytes, uint64_t *stats_dev, uint32_t mask_channels);
 int rbf_encode_runs(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
                     uint32_t nframes, uint32_t width, uint32_t height,
                     uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,

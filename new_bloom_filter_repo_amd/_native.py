@@ -67,10 +67,13 @@ _PROTOS = {
     "rbf_filter_stride_min": (_u64, [_u64]),
     "rbf_encode_runs_begin": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, ctypes.POINTER(Seeds),
                                      _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "rbf_encode_runs_begin_ex": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, ctypes.POINTER(Seeds),
+                                        _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u32]),
     "rbf_encode_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, ctypes.POINTER(Seeds),
                                _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double)]),
     "rbf_encode_gop_finish": (_int, [_vp, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double)]),
     "rbf_residual_mask_batch": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp]),
+    "rbf_residual_mask_batch_ex": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp, _u32]),
     "rbf_record_max_bytes": (_u64, [_u32, _u64]),
     "rbf_pack_records": (_int, [_vp, _u32, _u64, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double),
                                 _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64]),

@@ -749,8 +749,8 @@ static int launch_finish_ones(rbf_ctx *ctx, uint64_t *ones_dev, uint32_t pairs, 
 
 // every argument check of the mask stage, with no side effect (rbf_encode_gop_begin runs it before it touches the stream)
 static int check_mask_args(const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes, uint32_t width, uint32_t height,
-                           uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes, uint32_t sample_bytes, const int32_t *thr_floors,
-                           const void *masks_dev, uint64_t mask_stride_bytes, const uint64_t *ones_dev)
+                           uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes, uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
+                           const void *masks_dev, uint64_t mask_stride_bytes, const uint64_t *ones_dev, uint32_t mask_channels)
 {
     if (!frames_dev || !masks_dev || !ones_dev) return fail(RBF_EINVAL, "null device pointer");
     if (nframes < 2) return fail(RBF_EINVAL, "need at least 2 frames, got %u", nframes);
@@ -763,6 +763,13 @@ static int check_mask_args(const void *frames_dev, uint64_t frame_stride_bytes, 
     if (thr_floors)
         for (uint32_t i = 0; i + 1 < nframes; ++i)
             if (thr_floors[i] < 0) return fail(RBF_EINVAL, "negative threshold %d for pair %u", thr_floors[i], i);
+    if (mask_channels == 0) return fail(RBF_EINVAL, "mask_channels must be 1 (luma) or the number of samples the all-channel mask compares");
+    if (mask_channels >= 2) {                                     // the all-channel mask is lossless only: threshold 0, no table
+        if (thr_floor != 0 || thr_floors) return fail(RBF_EINVAL, "mask_channels %u: the all-channel mask takes no threshold (thr_floor %d, table %s)",
+                                                      mask_channels, thr_floor, thr_floors ? "given" : "none");
+        if ((uint64_t)mask_channels * sample_bytes > pixel_stride_bytes)
+            return fail(RBF_EINVAL, "mask_channels %u x %u-byte samples exceed the pixel stride %u", mask_channels, sample_bytes, pixel_stride_bytes);
+    }
     return RBF_OK;
 }
 
@@ -772,11 +779,13 @@ static int residual_mask_impl(rbf_ctx *ctx, const void *frames_dev, uint64_t fra
                               uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
                               void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev, bool finish,
                               const MaskFinish *gop_tail = nullptr /* rbf_encode_gop: publish + clears; fused into the mask kernel when it covers the frame */,
-                              const uint8_t *skip = nullptr /* rbf_encode_runs: skip[p] != 0 = pair p is not coded (zero row, zero count) */)
+                              const uint8_t *skip = nullptr /* rbf_encode_runs: skip[p] != 0 = pair p is not coded (zero row, zero count) */,
+                              uint32_t mask_channels = 1 /* >= 2: the all-channel mask over that many samples */)
 {
     if (int r = set_device(ctx)) return r;
     if (int r = check_mask_args(frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes,
-                                thr_floors, masks_dev, mask_stride_bytes, ones_dev)) return r;
+                                thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, mask_channels)) return r;
+    const bool any = mask_channels >= 2;
     const uint64_t n = (uint64_t)width * height;
     const uint32_t pairs = nframes - 1;
     if (ctx->ones_acc_cap < (size_t)pairs * 8) {
@@ -797,8 +806,10 @@ static int residual_mask_impl(rbf_ctx *ctx, const void *frames_dev, uint64_t fra
     // Fast path: flat frames, 16-byte aligned, whole 1024-pixel segments; the generic kernel does the rest.
     uint64_t fast_segs = 0;
     const bool flat = row_pitch_bytes == (uint64_t)width * pixel_stride_bytes;
-    const bool known = (sample_bytes == 1 && (pixel_stride_bytes == 1 || pixel_stride_bytes == 3)) ||
-                       (sample_bytes == 2 && (pixel_stride_bytes == 2 || pixel_stride_bytes == 6));
+    // (all-channel: 3 or 4 samples that fill the pixel; fewer samples than the pixel holds go to the generic kernel)
+    const bool known = any ? (mask_channels * sample_bytes == pixel_stride_bytes && (mask_channels == 3 || mask_channels == 4))
+                           : (sample_bytes == 1 && (pixel_stride_bytes == 1 || pixel_stride_bytes == 3)) ||
+                             (sample_bytes == 2 && (pixel_stride_bytes == 2 || pixel_stride_bytes == 6));
     if (!ctx->force_generic && flat && known && frame_stride_bytes % 16 == 0 && ((uintptr_t)frames_dev % 16) == 0 &&
         (size_t)pairs * 4 <= 48 * 1024)
         fast_segs = n / 1024;
@@ -887,11 +898,21 @@ static int residual_mask_impl(rbf_ctx *ctx, const void *frames_dev, uint64_t fra
                                (const uint8_t *)frames_dev, frame_stride_bytes, nframes, fast_segs, thr_floor, thr_tab_fast, (uint16_t *)masks_dev, \
                                mask_stride_bytes / 2, acc, mc, fin)
 #define RBF_MASK_GOP2(S, PB) do { if (thr0) RBF_MASK_GOP(S, PB, true); else RBF_MASK_GOP(S, PB, false); } while (0)
+#define RBF_MASK_ANY_GOP(S, PB) hipLaunchKernelGGL((k_residual_mask_any_gop<S, PB, true>), dim3(bx, chunks), dim3(WG_THREADS), lds, ctx->stream,   \
+                                (const uint8_t *)frames_dev, frame_stride_bytes, nframes, fast_segs, thr_tab_fast, (uint16_t *)masks_dev, \
+                                mask_stride_bytes / 2, acc, mc, fin)
         const bool thr0 = !thr_tab_fast && thr_floor == 0 && !(ctx->force_generic_mask_bits);     // "luma changed": no per-pixel extraction
-        if (sample_bytes == 1 && pixel_stride_bytes == 1) RBF_MASK_GOP2(uint8_t, 1);
+        if (any) {
+            if (pixel_stride_bytes == 3) RBF_MASK_ANY_GOP(uint8_t, 3);
+            else if (pixel_stride_bytes == 4) RBF_MASK_ANY_GOP(uint8_t, 4);
+            else if (pixel_stride_bytes == 6) RBF_MASK_ANY_GOP(uint16_t, 6);
+            else RBF_MASK_ANY_GOP(uint16_t, 8);
+        }
+        else if (sample_bytes == 1 && pixel_stride_bytes == 1) RBF_MASK_GOP2(uint8_t, 1);
         else if (sample_bytes == 1) RBF_MASK_GOP2(uint8_t, 3);
         else if (pixel_stride_bytes == 2) RBF_MASK_GOP2(uint16_t, 2);
         else RBF_MASK_GOP2(uint16_t, 6);
+#undef RBF_MASK_ANY_GOP
 #undef RBF_MASK_GOP2
 #undef RBF_MASK_GOP
     }
@@ -903,7 +924,13 @@ static int residual_mask_impl(rbf_ctx *ctx, const void *frames_dev, uint64_t fra
         if (bx > 65535) bx = 65535;
         dim3 grid((uint32_t)bx, pairs), block(WG_THREADS);
         LaunchTimer t(ctx, RBF_K_MASK);
-        if (sample_bytes == 1)
+        if (any && sample_bytes == 1)
+            hipLaunchKernelGGL(k_residual_mask_any<uint8_t>, grid, block, 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes,
+                               width, n, row_pitch_bytes, pixel_stride_bytes, mask_channels, thr_tab, (uint64_t *)masks_dev, mask_stride_bytes / 8, acc, first_word);
+        else if (any)
+            hipLaunchKernelGGL(k_residual_mask_any<uint16_t>, grid, block, 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes,
+                               width, n, row_pitch_bytes, pixel_stride_bytes, mask_channels, thr_tab, (uint64_t *)masks_dev, mask_stride_bytes / 8, acc, first_word);
+        else if (sample_bytes == 1)
             hipLaunchKernelGGL(k_residual_mask<uint8_t>, grid, block, 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes,
                                width, n, row_pitch_bytes, pixel_stride_bytes, thr_floor, thr_tab, (uint64_t *)masks_dev, mask_stride_bytes / 8, acc, first_word);
         else
@@ -924,8 +951,18 @@ int rbf_residual_mask_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame
                             uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
                             void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev)
 {
+    return rbf_residual_mask_batch_ex(ctx, frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes,
+                                      thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, 1);
+}
+
+int rbf_residual_mask_batch_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                               uint32_t nframes, uint32_t width, uint32_t height,
+                               uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
+                               uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
+                               void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev, uint32_t mask_channels)
+{
     return residual_mask_impl(ctx, frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes,
-                              thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, true);
+                              thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, true, nullptr, nullptr, mask_channels);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1392,13 +1429,27 @@ int rbf_encode_runs_begin(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_s
                           void *filters_dev, uint64_t filter_stride_bytes,
                           void *witnesses_dev, uint64_t witness_stride_bytes, uint64_t *stats_dev)
 {
+    return rbf_encode_runs_begin_ex(ctx, frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes,
+                                    thr_floor, thr_floors, run_starts, seeds, masks_dev, mask_stride_bytes, ones_dev, filters_dev, filter_stride_bytes,
+                                    witnesses_dev, witness_stride_bytes, stats_dev, 1);
+}
+
+int rbf_encode_runs_begin_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                             uint32_t nframes, uint32_t width, uint32_t height,
+                             uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
+                             uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
+                             const uint8_t *run_starts, const rbf_seeds *seeds,
+                             void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev,
+                             void *filters_dev, uint64_t filter_stride_bytes,
+                             void *witnesses_dev, uint64_t witness_stride_bytes, uint64_t *stats_dev, uint32_t mask_channels)
+{
     if (!ctx) return fail(RBF_EINVAL, "null context");
     if (ctx->gop.active) return fail(RBF_EINVAL, "rbf_encode_runs_begin / rbf_encode_gop_begin: the previous block of this context has not been finished (rbf_encode_gop_finish)");
     if (!filters_dev || !witnesses_dev || !stats_dev || !seeds) return fail(RBF_EINVAL, "null pointer");
     if (int r = set_device(ctx)) return r;
     // nothing below this block has run, and nothing of the caller's has been touched, when an argument is bad
     if (int r = check_mask_args(frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes,
-                                thr_floors, masks_dev, mask_stride_bytes, ones_dev)) return r;
+                                thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, mask_channels)) return r;
     const uint32_t pairs = nframes - 1;
     const uint64_t n = (uint64_t)width * height;
     if (witness_stride_bytes % 8 || witness_stride_bytes < ((n + 63) / 64) * 8) return fail(RBF_EINVAL, "witness stride too small or misaligned");
@@ -1439,7 +1490,7 @@ int rbf_encode_runs_begin(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_s
     tail.clear_b = (uint4 *)stats_dev;     tail.quads_b = (uint64_t)pairs * RBF_STATS_PER_FRAME * 8 / 16;
     if (int r = residual_mask_impl(ctx, frames_dev, frame_stride_bytes, nframes, width, height, row_pitch_bytes,
                                    pixel_stride_bytes, sample_bytes, thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, false, &tail,
-                                   has_skip ? ctx->run_skip.data() : nullptr))
+                                   has_skip ? ctx->run_skip.data() : nullptr, mask_channels))
         return r;
     rbf_ctx::PendingGop &g = ctx->gop;
     g.active = true; g.token = token; g.n = n; g.pairs = pairs; g.seeds = *seeds; g.has_skip = has_skip;

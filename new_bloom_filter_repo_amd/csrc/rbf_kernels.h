@@ -94,6 +94,45 @@ __global__ __launch_bounds__(WG_THREADS) void k_residual_mask(
     }
 }
 
+// All-channel twin of k_residual_mask (mask_channels >= 2, threshold 0): bit = "any of the pixel's first `channels` samples differs"
+// (exact, no int16 rule).  thr: 0 = code the pair; the host's skip marker INT32_MAX (a pair in front of a keyframe) gives a zero row.
+template <typename SAMPLE>
+__global__ __launch_bounds__(WG_THREADS) void k_residual_mask_any(
+    const uint8_t *__restrict__ frames, uint64_t frame_stride, uint32_t width, uint64_t n,
+    uint64_t row_pitch, uint32_t pixel_stride, uint32_t channels, const int32_t *__restrict__ thr_tab /* nullable: per pair */,
+    uint64_t *__restrict__ masks, uint64_t mask_stride_words, uint64_t *__restrict__ ones, uint64_t first_word)
+{
+    __shared__ uint32_t wave_ones[WG_WAVES];
+    const uint32_t f = blockIdx.y;
+    const bool coded = !thr_tab || thr_tab[f] <= 0;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint8_t *prev = frames + (uint64_t)f * frame_stride;
+    const uint8_t *curr = prev + frame_stride;
+    uint64_t *mask = masks + (uint64_t)f * mask_stride_words;
+    const uint64_t nwords = (n + 63) >> 6;
+    uint32_t cnt = 0;
+    for (uint64_t w = first_word + (uint64_t)blockIdx.x * WG_WAVES + wave; w < nwords; w += (uint64_t)gridDim.x * WG_WAVES) {
+        const uint64_t i = w * 64 + lane;
+        bool bit = false;
+        if (coded && i < n) {
+            const uint64_t y = i / width, x = i - y * width;
+            const SAMPLE *a = (const SAMPLE *)(prev + y * row_pitch + x * pixel_stride);
+            const SAMPLE *b = (const SAMPLE *)(curr + y * row_pitch + x * pixel_stride);
+            for (uint32_t c = 0; c < channels; ++c) bit |= a[c] != b[c];
+        }
+        const uint64_t word = __ballot(bit);
+        cnt += __popcll(word);
+        if (lane == 0) mask[w] = flip_bytes64(word);
+    }
+    if (lane == 0) wave_ones[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int k = 0; k < WG_WAVES; ++k) s += wave_ones[k];
+        if (s) atomicAdd((unsigned long long *)&ones[f], (unsigned long long)s);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // A4  insert: every '1' position of the mask sets its probe bits (add_index, :99-114)
 // ------------------------------------------------------------------------------------------

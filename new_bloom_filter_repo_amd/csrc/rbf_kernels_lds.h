@@ -897,6 +897,62 @@ __device__ __forceinline__ uint32_t lane_bits_thr0(const LanePixels<SAMPLE, PIXE
     return bits;
 }
 
+// All-channel mode (rbf_residual_mask_batch_ex with mask_channels = the pixel's sample count; threshold 0 only): the bit is "some byte of
+// the pixel changed", an exact comparison of every sample -- a 16-bit change of 0x8000, which the int16 rule above ignores, IS marked.  The
+// pixel's bytes are XOR-ed as whole dwords and reduced to one flag without extracting a sample.  3-byte pixels: the three bytes of each
+// of four pixels are gathered into three dwords (v_perm) whose OR goes through the carry trick above.  4- and 8-byte pixels: a pixel is
+// one or two whole dwords, its flag one v_min_u32 against 1 (asm: the compiler turns a visible min(t, 1) into v_cmp + v_cndmask).
+// 6-byte pixels: the three halves of each of two pixels are gathered into three dwords (one half per pixel each), OR-ed, and from there on
+// it is the planar 16-bit path above (v_pk_min_u16, accumulator, interleave).
+template <typename SAMPLE, int PIXEL_BYTES>
+__device__ __forceinline__ uint32_t lane_bits_any(const LanePixels<SAMPLE, PIXEL_BYTES> &a, const LanePixels<SAMPLE, PIXEL_BYTES> &b, uint32_t one2, uint32_t &count_src)
+{
+    static_assert(PIXEL_BYTES == 3 || PIXEL_BYTES == 4 || PIXEL_BYTES == 6 || PIXEL_BYTES == 8, "all-channel masks: 3 or 4 samples of 1 or 2 bytes");
+    uint32_t bits = 0;
+    if (PIXEL_BYTES == 3) {
+        constexpr int shift_of_group[4] = {4, 0, 12, 8};       // as lane_bits_thr0
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {                           // pixels 4g..4g+3 = bytes 0-2 | 3-5 | 6-8 | 9-11 of three dwords
+            const uint32_t x0 = a.d[3 * g] ^ b.d[3 * g], x1 = a.d[3 * g + 1] ^ b.d[3 * g + 1], x2 = a.d[3 * g + 2] ^ b.d[3 * g + 2];
+            const uint32_t s0 = __builtin_amdgcn_perm(x2, __builtin_amdgcn_perm(x1, x0, 0x00060300u), 0x05020100u);   // bytes 0, 3, 6, 9
+            const uint32_t s1 = __builtin_amdgcn_perm(x2, __builtin_amdgcn_perm(x1, x0, 0x00070401u), 0x06020100u);   // bytes 1, 4, 7, 10
+            const uint32_t s2 = __builtin_amdgcn_perm(x2, __builtin_amdgcn_perm(x1, x0, 0x00000502u), 0x07040100u);   // bytes 2, 5, 8, 11
+            const uint32_t z = s0 | s1 | s2;
+            const uint32_t f = (((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z) & 0x80808080u;
+            bits |= (((f >> 7) * 0x08040201u) >> 24) << shift_of_group[g];
+        }
+        count_src = bits;
+    } else if (PIXEL_BYTES == 4 || PIXEL_BYTES == 8) {
+        constexpr int DPP = PIXEL_BYTES / 4;                    // dwords per pixel
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            uint32_t t = a.d[DPP * k] ^ b.d[DPP * k];
+            if (DPP == 2) t |= a.d[DPP * k + 1] ^ b.d[DPP * k + 1];
+            uint32_t g;
+            asm("v_min_u32 %0, 1, %1" : "=v"(g) : "v"(t));
+            bits |= g << (k ^ 7);                               // MSB-first within each byte
+        }
+        count_src = bits;
+    } else {
+        uint32_t acc = 0;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int j = s ^ 4;                                // pixels 2j, 2j+1 = halves 0-2 | 3-5 of dwords 3j..3j+2
+            const uint32_t x0 = a.d[3 * j] ^ b.d[3 * j], x1 = a.d[3 * j + 1] ^ b.d[3 * j + 1], x2 = a.d[3 * j + 2] ^ b.d[3 * j + 2];
+            const uint32_t h0 = __builtin_amdgcn_perm(x1, x0, 0x07060100u);       // {half 0, half 3}
+            const uint32_t h1 = __builtin_amdgcn_perm(x2, x0, 0x05040302u);       // {half 1, half 4}
+            const uint32_t h2 = __builtin_amdgcn_perm(x2, x1, 0x07060100u);       // {half 2, half 5}
+            const uint32_t t = h0 | h1 | h2;
+            uint32_t g;
+            asm("v_pk_min_u16 %0, %1, %2" : "=v"(g) : "v"(t), "v"(one2));
+            acc = (acc << 2) | g;
+        }
+        bits = (acc >> 16) | (acc << 1);
+        count_src = acc;
+    }
+    return bits;
+}
+
 // What used to be k_finish_ones' job, folded into the mask kernel when it covers the whole frame (rbf_encode_gop on frames of whole
 // 1024-pixel segments): every workgroup clears its share of up to two output regions (round 5: only the stats of the batch -- the
 // witness rows are no longer cleared, k_chunk_offsets zeroes the few words compaction ORs into; region a is null), and
@@ -933,146 +989,23 @@ __global__ __launch_bounds__(WG_THREADS) void k_residual_mask_gop(
     uint16_t *__restrict__ masks, uint64_t mask_stride_u16, uint64_t *__restrict__ ones,
     const MaskChunks chunks, const MaskFinish fin)
 {
-    // blockIdx.y = temporal chunk: frames [f0, f1] (f1 - f0 pairs); chunks of one run overlap by one frame, which
-    // buys gridDim.y times more waves in flight for ~gridDim.y/nframes extra reads
-    extern __shared__ uint32_t cnt[];                          // [nframes-1] per-workgroup ones
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t seg = (uint64_t)blockIdx.x * WG_WAVES + wave;
-    uint32_t f0, f1;
-    bool skipped = false;
-    if (chunks.count) {
-        const uint32_t c = chunks.pairs[blockIdx.y];
-        f0 = chunks.first[blockIdx.y];
-        f1 = f0 + (c & (MASK_CHUNK_SKIP - 1u));
-        skipped = (c & MASK_CHUNK_SKIP) != 0u;
-    } else {
-        f0 = blockIdx.y * chunks.ppc;
-        f1 = f0 + chunks.ppc < nframes - 1 ? f0 + chunks.ppc : nframes - 1;
-    }
-    for (uint32_t i = threadIdx.x; i + 1 < nframes; i += WG_THREADS) cnt[i] = 0;
-    __syncthreads();
-    if (skipped) {
-        if (seg < nsegs)
-            for (uint32_t f = f0; f < f1; ++f) masks[seg * 64 + lane + (uint64_t)f * mask_stride_u16] = 0;
-    } else if (seg < nsegs && f0 < f1) {
-        using LP = LanePixels<SAMPLE, PIXEL_BYTES>;
-        const uint64_t lane_off = (seg * 1024 + (uint64_t)lane * 16) * PIXEL_BYTES;
-        const uint8_t *p = frames + lane_off;
-        uint16_t *out = masks + seg * 64 + lane;
-        uint32_t one2;
-        asm volatile("v_mov_b32 %0, 0x10001" : "=v"(one2));
-        LP fa, fb, fc, fd;                                        // four frames in registers, roles rotate: TWO loads are in flight while a pair is compared
-        fa.template load<NT>(p + (uint64_t)f0 * frame_stride);
-        fb.template load<NT>(p + (uint64_t)(f0 + 1) * frame_stride);
-        if (f0 + 2 <= f1) fc.template load<NT>(p + (uint64_t)(f0 + 2) * frame_stride);
-        // pair (prev, cur) = mask f-1; `nxt2` receives frame f+2 meanwhile (frame f+1 is already on its way).  Returns a value whose
-        // population count is this lane's number of set bits.
-        auto step = [&](const LP &prev, const LP &cur, LP &nxt2, uint32_t f) -> uint32_t {
-            if (f + 2 <= f1) nxt2.template load<NT>(p + (uint64_t)(f + 2) * frame_stride);
-            const int32_t thr = thr_tab ? thr_tab[f - 1] : thr_all;
-            uint32_t bits = 0, csrc = 0;
-            if (THR0) bits = lane_bits_thr0<SAMPLE, PIXEL_BYTES>(prev, cur, one2, csrc);      // host: no per-pair table and thr == 0
-            else {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const bool b = residual_bit<SAMPLE>((SAMPLE)prev.luma(k), (SAMPLE)cur.luma(k), thr);
-                    bits |= (b ? 1u : 0u) << (k ^ 7);         // MSB-first within each byte
-                }
-                csrc = bits;
-            }
-            out[(uint64_t)(f - 1) * mask_stride_u16] = (uint16_t)bits;
-            return csrc;
-        };
-        // The wave's counts stay in ONE register until the chunk ends: lane s of `tally` holds the ones of pairs base + 2s (low half) and
-        // base + 2s + 1 (high half).  Two pairs share a DPP tree (their lane counts ride as packed 16-bit halves, each total <= 1024),
-        // v_readlane hands the packed totals to the scalar unit and ONE v_writelane files them.  Round 5 did a six-step tree, a compare, two exec
-        // masks and the compiler's uniform-address atomic loop (~8 vector + ~15 scalar instructions and an LDS atomic) PER PAIR -- in a
-        // kernel that runs underneath the issue-bound insert / query kernels of the neighbouring pipelines, where every instruction it
-        // issues is one of theirs that waits.
-        uint32_t tally = 0, base = f0;
-        auto flush = [&]() {
-            const uint32_t i = base + 2u * lane;
-            if (i < f1 && (tally & 0xFFFFu)) atomicAdd(&cnt[i], tally & 0xFFFFu);     // (per-lane addresses: one ds_add_u32 for the wave)
-            if (i + 1u < f1 && (tally >> 16)) atomicAdd(&cnt[i + 1u], tally >> 16);
-            tally = 0;
-        };
-        auto file2 = [&](uint32_t c_even, uint32_t c_odd, uint32_t f) {               // counts of pairs f-1 and f
-            const uint32_t tot = wave_sum_to_lane63(__popc(c_even) | (__popc(c_odd) << 16));
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tot, 63);
-            const uint32_t slot = (f - 1u - base) >> 1;                               // < 64 (scalar: f and base are uniform)
-            uint32_t keep;
-            // v_writelane takes ONE SGPR over the constant bus, so the lane select rides in M0 (reserved: saved and restored, as RowDmaC does)
-            asm volatile("s_mov_b32 %1, m0\n\t"
-                         "s_mov_b32 m0, %3\n\t"
-                         "s_nop 0\n\t"
-                         "v_writelane_b32 %0, %2, m0\n\t"
-                         "s_mov_b32 m0, %1"
-                         : "+v"(tally), "=&s"(keep) : "s"(t), "s"(slot));
-        };
-        // unrolled by four so that the rotation prev <- cur <- nxt <- nxt2 costs no register moves
-        for (uint32_t f = f0 + 1; f <= f1; f += 4) {
-            if (f - 1u - base == 2u * WAVE) { flush(); base += 2u * WAVE; }
-            const uint32_t c0 = step(fa, fb, fd, f);
-            const uint32_t c1 = f + 1 <= f1 ? step(fb, fc, fa, f + 1) : 0u;
-            file2(c0, c1, f);
-            if (f + 2 <= f1) {
-                const uint32_t c2 = step(fc, fd, fb, f + 2);
-                const uint32_t c3 = f + 3 <= f1 ? step(fd, fa, fc, f + 3) : 0u;
-                file2(c2, c3, f + 2);
-            }
-        }
-        flush();
-    }
-    __syncthreads();
-    for (uint32_t i = f0 + threadIdx.x; i < f1; i += WG_THREADS)
-        if (cnt[i]) atomicAdd((unsigned long long *)&ones[i], (unsigned long long)cnt[i]);
-    if (!fin.enabled) return;
-    // ---- the tail of the pass (see MaskFinish).  Only wave 0 -- whose lanes issued the workgroup's count atomics -- takes a ticket.
-    const uint64_t wg = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, nwg = (uint64_t)gridDim.x * gridDim.y;
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const bool wide = f1 > f0 + WAVE;              // (workgroup-uniform) more than 64 pairs in this chunk: waves 1..3 issued count atomics too
-    if (wide) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    if (wave != 0) {                               // waves 1..3: their share of the clears, and out
-        for (uint64_t i = wg * WG_THREADS + threadIdx.x; i < fin.quads_a; i += nwg * WG_THREADS) fin.clear_a[i] = z;
-        for (uint64_t i = wg * WG_THREADS + threadIdx.x; i < fin.quads_b; i += nwg * WG_THREADS) fin.clear_b[i] = z;
-        return;
-    }
-    // My counts must have been performed before my ticket is.  They are agent-scope atomics (carried out at the device's coherence
-    // point, not in this XCD's L2), so waiting for their acknowledgements is enough -- a __threadfence() here writes the L2 back
-    // from every workgroup and made the kernel 8x slower (25 -> 190 us).
-    if (!wide) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // Two-level ticket: all ~2 000 workgroups of a 1080p GOP are resident at once and finish together, and returning atomics on ONE
-    // address complete one every ~6 ns -- a single counter cost the kernel 13 us.  64 first-level counters (workgroup id mod 64),
-    // whose last arrivals meet on a second-level one.
-    uint32_t is_last = 0;
-    if (lane == 0) {
-        const uint32_t idx = (uint32_t)(wg % MASK_TICKETS);
-        const uint32_t mine = (uint32_t)((nwg + MASK_TICKETS - 1 - idx) / MASK_TICKETS);      // workgroups on this counter
-        if (atomicAdd(fin.ticket + idx, 1u) == mine - 1u) {
-            __hip_atomic_store(fin.ticket + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t groups = nwg < MASK_TICKETS ? (uint32_t)nwg : (uint32_t)MASK_TICKETS;
-            is_last = atomicAdd(fin.ticket + MASK_TICKETS, 1u) == groups - 1u ? 1u : 0u;
-        }
-    }
-    is_last = __builtin_amdgcn_readfirstlane(is_last);
-    for (uint64_t i = wg * WG_THREADS + threadIdx.x; i < fin.quads_a; i += nwg * WG_THREADS) fin.clear_a[i] = z;
-    for (uint64_t i = wg * WG_THREADS + threadIdx.x; i < fin.quads_b; i += nwg * WG_THREADS) fin.clear_b[i] = z;
-    if (!is_last) return;
-    // the last workgroup: counts out (to the caller's array and the host), accumulator and ticket back to zero
-    for (uint32_t i = lane; i < fin.count; i += WAVE) {
-        const uint64_t v = __hip_atomic_load(&ones[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (the other workgroups added at the coherence point)
-        fin.ones_out[i] = v;
-        __hip_atomic_store(&ones[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (fin.host_block) __hip_atomic_store(&fin.host_block[1 + i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (fin.host_block) {
-        __threadfence_system();
-        if (lane == 0) __hip_atomic_store(&fin.host_block[0], fin.token, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (lane == 0) __hip_atomic_store(fin.ticket + MASK_TICKETS, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    constexpr bool ANY = false;
+#include "rbf_kernels_mask_body.h"
+}
+
+// All-channel twin of k_residual_mask_gop (rbf_residual_mask_batch_ex / rbf_encode_runs_begin_ex with mask_channels >= 2): the same
+// chunks, skipped pairs, packed-count tally and fused finish; the bit is "any sample of the pixel changed" (lane_bits_any).  thr_tab:
+// nullable, 0 = code the pair, > 0 = a skipped pair (a block with more runs than the chunk table holds).
+template <typename SAMPLE, int PIXEL_BYTES, bool NT = false>
+__global__ __launch_bounds__(WG_THREADS) void k_residual_mask_any_gop(
+    const uint8_t *__restrict__ frames, uint64_t frame_stride, uint32_t nframes, uint64_t nsegs /* of 1024 px */,
+    const int32_t *__restrict__ thr_tab /* nullable: per pair */,
+    uint16_t *__restrict__ masks, uint64_t mask_stride_u16, uint64_t *__restrict__ ones,
+    const MaskChunks chunks, const MaskFinish fin)
+{
+    constexpr bool ANY = true, THR0 = false;
+    constexpr int32_t thr_all = 0;
+#include "rbf_kernels_mask_body.h"
 }
 
 }  // namespace rbf

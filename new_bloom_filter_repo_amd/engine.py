@@ -57,12 +57,25 @@ class BloomEngine:
         every pair, a sequence of F-1 numbers, or None with adaptive=(noise_tolerance, min_thr,
         max_thr) for the reference's per-frame noise-adaptive threshold (:746-766).  Returns
         (masks_packed uint8 [F-1, stride], ones uint64 [F-1]); masks stay on the device as well
-        for the following encode."""
+        for the following encode.
+        luma_only=False: the all-channel mask (rbf_residual_mask_batch_ex) -- a pixel's bit is 1 when ANY of its C samples changed,
+        compared exactly (a 16-bit change of 0x8000 is marked).  Lossless only: threshold must be 0, no table, no adaptive."""
+        if not luma_only and (adaptive is not None or threshold is None or np.ndim(threshold) != 0 or float(threshold) != 0.0):
+            raise ValueError("the all-channel mask (luma_only=False) is lossless only: threshold must be 0, got %r%s"
+                             % (threshold, " with adaptive" if adaptive is not None else ""))
+        if not luma_only and (np.ndim(frames) != 4 or np.shape(frames)[3] < 2):
+            raise ValueError("the all-channel mask needs (F, H, W, C) frames with C >= 2 samples per pixel")
         fb, F, H, W, C, sb = self._upload_frames(frames, 2)
         n = H * W
         stride = nat.packed_stride(n)
         mb = self._buf("masks", (F - 1) * stride)
         ob = self._buf("ones", (F - 1) * 8)
+        if not luma_only:
+            nat.check(nat.lib().rbf_residual_mask_batch_ex(
+                self.ctx.handle, fb.ptr, H * W * C * sb, F, W, H, W * C * sb, C * sb, sb, 0, None, mb.ptr, stride, ob.ptr, C))
+            self.thresholds = [0] * (F - 1)
+            self.n, self.mask_stride = n, stride
+            return mb.download((F - 1) * stride).reshape(F - 1, stride), ob.download((F - 1) * 8, dtype=np.uint64).copy()
         if threshold is None:
             if adaptive is None:
                 raise ValueError("threshold=None needs adaptive=(noise_tolerance, min_thr, max_thr)")

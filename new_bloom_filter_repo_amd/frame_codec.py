@@ -247,7 +247,13 @@ def parse_record(wire_format, compressed_data):
 class VideoFrameCompressor:
     def __init__(self, noise_tolerance=10.0, keyframe_interval=30, min_diff_threshold=3.0,
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, num_threads=None,
-                 use_direct_yuv=False, verbose=False, wire_format="f64", ctx=None):
+                 use_direct_yuv=False, verbose=False, wire_format="f64", ctx=None, mask_channels="luma"):
+        """mask_channels: "luma" (default) -- the reference's residual mask on the luma plane; "all" -- a pixel's bit is 1 when ANY of its
+        samples changed (rbf_residual_mask_batch_ex), so that the (mask, all channels) record is lossless even where only chroma moved.
+        "all" is lossless only: _calculate_frame_diff takes threshold 0 and nothing else."""
+        if mask_channels not in ("luma", "all"):
+            raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
+        self.mask_channels = mask_channels
         self.noise_tolerance = noise_tolerance
         self.keyframe_interval = keyframe_interval
         self.min_diff_threshold = min_diff_threshold
@@ -310,8 +316,19 @@ class VideoFrameCompressor:
 
     def _calculate_frame_diff(self, prev_frame, curr_frame, threshold=None):
         """(binary_diff HxW uint8, changed_values, density) -- improved_video_compressor.py:768-847.
-        threshold=None: noise-adaptive threshold of the current luma plane (:804-805)."""
+        threshold=None: noise-adaptive threshold of the current luma plane (:804-805).
+        mask_channels="all": the all-channel mask of the full frames at threshold 0 (anything else raises ValueError)."""
+        if self.mask_channels == "all" and (threshold is None or np.ndim(threshold) != 0 or float(threshold) != 0.0):
+            raise ValueError("mask_channels='all' is lossless only: threshold must be 0, got %r" % (threshold,))
         a, b, is_color = self._luma_pair(prev_frame, curr_frame)
+        if self.mask_channels == "all" and is_color:
+            masks, ones = self._engine.residual_masks(np.stack([a, b]), 0, luma_only=False)
+            h, w = a.shape[:2]
+            n = h * w
+            packed = masks[0][:(n + 7) // 8]
+            values = gather_values(self._ctx, b, packed)
+            binary_diff = np.unpackbits(packed)[:n].reshape(h, w)
+            return binary_diff, values, np.uint64(ones[0]) / binary_diff.size
         ya, yb = self._luma_planes(a, b, is_color)
         if threshold is None:
             threshold = self._adaptive_diff_threshold(yb)

@@ -61,7 +61,7 @@ class GopCoder:
 
     def __init__(self, ctx, width, height, nframes, channels=3, sample_bytes=1, seeds=P.SEEDS_VIDEO,
                  allocator=None, threshold=0.0, out_allocator=None, frames_block=None, adaptive=None,
-                 planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None):
+                 planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None, mask_channels=1):
         """allocator: device memory source (default: library-owned); out_allocator: separate source for
         the output record (filters, witnesses, stats); frames_block: share another coder's frame buffer.
         threshold=None with adaptive=(noise_tolerance, min_thr, max_thr): per-frame noise-adaptive
@@ -74,8 +74,20 @@ class GopCoder:
         run_starts: frame indices (within the block of `nframes` frames) that are KEYFRAMES of the caller's stream: each starts a new run,
         and the pair in front of it is not coded (rbf_encode_runs: several GOPs in ONE launch sequence; results() marks those pairs
         `skipped`).  The reference codes frame by frame (improved_video_compressor.py:198-266); batching whole GOPs is this package's.
+        mask_channels: 1 (default) = the luma mask; >= 2 = the all-channel mask (rbf_encode_runs_begin_ex): a pixel's bit is 1 when any of
+        its first mask_channels samples changed.  Lossless only: threshold 0, no adaptive thresholds, interleaved frames (not planar_luma).
         """
         from .engine import threshold_floor
+        self.mask_channels = int(mask_channels)
+        if not 1 <= self.mask_channels <= channels:
+            raise ValueError("mask_channels must be 1 (luma) or up to the %d samples of a pixel, got %r" % (channels, mask_channels))
+        if self.mask_channels > 1:
+            if planar_luma:
+                raise ValueError("the all-channel mask reads the interleaved frames: not with planar_luma")
+            if threshold is None or adaptive is not None:
+                raise ValueError("the all-channel mask is lossless only: no adaptive thresholds")
+            if not np.ndim(threshold) == 0 or float(threshold) != 0.0:
+                raise ValueError("the all-channel mask is lossless only: threshold must be 0, got %r" % (threshold,))
         self.ctx, self.W, self.H, self.F, self.C, self.sb = ctx, width, height, nframes, channels, sample_bytes
         self.n = width * height
         self.pairs = nframes - 1
@@ -221,11 +233,11 @@ class GopCoder:
             src, fstride, pitch, pstride = self.luma.ptr + gop * self.luma_bytes * self.F, self.luma_bytes, self.W * self.sb, self.sb
         else:
             src, fstride, pitch, pstride = self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.W * self.C * self.sb, self.C * self.sb
-        nat.check(nat.lib().rbf_encode_runs_begin(
+        nat.check(nat.lib().rbf_encode_runs_begin_ex(
             self.ctx.handle, src, fstride, self.F, self.W, self.H,
             pitch, pstride, self.sb, self.thr, self.thr_tab, self.run_starts, ctypes.byref(self.seeds),
             self.masks.ptr, self.mask_stride, self.ones.ptr,
-            self.filters.ptr, self.filter_stride, self.witness.ptr, self.witness_stride, self.stats.ptr))
+            self.filters.ptr, self.filter_stride, self.witness.ptr, self.witness_stride, self.stats.ptr, self.mask_channels))
 
     def encode_ready(self):
         """True once the mask stage's counts have reached the host (encode_finish will not wait)."""

@@ -74,3 +74,75 @@ def make_clip_shard(seed, width, height, first, stop, interval=30, p=P_KSTAR_2_3
 def make_mask(seed, n, p):
     """Flat 0/1 uint8 vector with Bernoulli(p) ones (the reference's `binary_input`)."""
     return (np.random.default_rng(seed).random(n) < p).astype(np.uint8)
+
+
+def _rgb_to_yuv444(rgb, bits):
+    """BT.601 full-range RGB -> YUV444 with rounding, per pixel: float (..., 3) RGB in the sample range -> integer (..., 3) YUV."""
+    mid, top = float(1 << (bits - 1)), (1 << bits) - 1
+    r, g, b = rgb[..., 0], rgb[..., 1], rgb[..., 2]
+    y = 0.299 * r + 0.587 * g + 0.114 * b
+    u = mid - 0.168736 * r - 0.331264 * g + 0.5 * b
+    v = mid + 0.5 * r - 0.418688 * g - 0.081312 * b
+    return np.clip(np.rint(np.stack([y, u, v], axis=-1)), 0, top)
+
+
+def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, color_space="YUV"):
+    """nframes (H, W, 3) frames that change the way camera footage does, unlike make_gop: a smooth RGB texture of which a Bernoulli(moving)
+    set of pixels is perturbed by a few levels per channel in every pair, then converted to YUV444 (BT.601, rounded) -- so in every pair
+    some pixels change in chroma while their luma stays the same (the luma residual mask misses them).  color_space="BGR" returns the RGB
+    frames in B, G, R order before the conversion (channel 0 = B: some pixels change in G or R only).  16-bit: the samples are scaled to 16
+    bits over a fixed fine texture, and in every pair a few channel-0 samples change by exactly 0x8000 (the int16 rule's blind spot)."""
+    if color_space not in ("YUV", "BGR"):
+        raise ValueError("color_space must be 'YUV' or 'BGR'")
+    rng = np.random.default_rng(seed)
+    dtype = np.dtype(dtype)
+    bits = 8 * dtype.itemsize
+    scale = 257.0 if bits == 16 else 1.0
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    rgb = np.empty((height, width, 3), dtype=np.float64)
+    for c in range(3):                           # a few low-frequency waves and a gradient per channel: smooth, no two channels alike
+        ph, fx, fy = rng.uniform(0, 2 * np.pi, 3), rng.uniform(0.5, 3.0, 3), rng.uniform(0.5, 3.0, 3)
+        wave = sum(np.sin(2 * np.pi * (fx[i] * xx / width + fy[i] * yy / height) + ph[i]) for i in range(3))
+        rgb[..., c] = 128.0 + 30.0 * wave + 40.0 * (xx / width - yy / height)
+    top = (1 << bits) - 1
+    rgb = np.clip(np.rint(rgb), 0, 255) * scale  # the scene, in sample units
+    if bits == 16:
+        rgb += rng.integers(0, 256, (height, width, 3))          # a fixed sub-level texture of a 16-bit sensor
+
+    def render(x):
+        return x if color_space == "BGR" else _rgb_to_yuv444(x, bits)
+
+    cur = render(rgb)
+    flip = np.zeros((height, width), dtype=bool)     # 16-bit: channel-0 samples currently offset by 0x8000
+    frames = []
+
+    def emit(img):
+        f = np.ascontiguousarray(img[..., ::-1] if color_space == "BGR" else img).astype(dtype)
+        if bits == 16:
+            f[..., 0] ^= (flip * 0x8000).astype(np.uint16)
+        frames.append(f)
+    emit(cur)
+    n = width * height
+    for _ in range(nframes - 1):
+        idx = np.flatnonzero(rng.random(n) < moving)
+        if idx.size == 0:
+            idx = rng.integers(0, n, 1)
+        ys, xs = np.unravel_index(idx, (height, width))
+        d = rng.integers(-6, 7, (idx.size, 3))
+        d[np.all(d == 0, axis=1), 1] = 1                                   # every chosen pixel moves
+        d = d * scale
+        d[0] = (3, 0, -8) if color_space == "YUV" else (2, -1, 0)          # luma kept, chroma moved -- at least once per pair (BGR: B = RGB[2])
+        lv = np.clip(rgb[ys, xs] + d, 0, top)
+        if color_space == "YUV":
+            old = _rgb_to_yuv444(rgb[ys[0], xs[0]], bits)
+            for _ in range(64):                                              # nudge pixel 0 until its Y rounds to the same value
+                new = _rgb_to_yuv444(lv[0], bits)
+                if new[0] == old[0] and np.any(new[1:] != old[1:]):
+                    break
+                lv[0] = np.clip(rgb[ys[0], xs[0]] + rng.integers(-8, 9, 3) * np.array([1, 0, 1]), 0, top)
+        rgb[ys, xs] = lv
+        cur[ys, xs] = render(lv)                     # (emit copies)
+        if bits == 16:
+            flip.reshape(-1)[rng.integers(0, n, 3)] ^= True
+        emit(cur)
+    return frames

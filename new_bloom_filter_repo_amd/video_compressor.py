@@ -5,7 +5,8 @@ through the GPU Bloom path (VideoFrameCompressor).
 
 Losslessness is kept unconditional, as the reference promises ("True Lossless"): an inter-frame is
 only emitted when applying its record to frame t-1 reproduces frame t bit for bit (the luma mask at
-threshold 0 must cover every changed pixel); otherwise that frame falls back to a keyframe.
+threshold 0 must cover every changed pixel); otherwise that frame falls back to a keyframe.  mask_channels="all" codes the
+mask of every pixel in which any sample changed instead, which covers every change by construction.
 
 Container: all-keyframe streams are written exactly as the reference does -- 'BFVC' | <I frames |
 (<I len | record)* (:398-406) -- so either implementation reads them.  Streams with inter-frames use
@@ -60,16 +61,16 @@ class _Lane:
         self.coders = {}
         self.engine = None
 
-    def coder(self, W, H, F, C, sb):
+    def coder(self, W, H, F, C, sb, mask_channels=1):
         from .gop import GopCoder
-        key = (W, H, F, C, sb)
+        key = (W, H, F, C, sb, mask_channels)
         c = self.coders.get(key)
         if c is None:
             if len(self.coders) >= 2:            # a stream has at most two block sizes (full blocks and its tail)
                 for old in self.coders.values():
                     old.close()
                 self.coders = {}
-            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb)
+            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels)
         return c
 
     def decode_engine(self):
@@ -109,8 +110,8 @@ class ImprovedVideoCompressor:
     def __init__(self, noise_tolerance=10.0, keyframe_interval=30, min_diff_threshold=3.0,
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
-                 gop_batching=True, block_frames=None, gpu_lanes=2):
-        """Reference signature (improved_video_compressor.py:318-327) plus five keyword-only extras:
+                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma"):
+        """Reference signature (improved_video_compressor.py:318-327) plus six keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -119,7 +120,14 @@ class ImprovedVideoCompressor:
         inter_frames -- None (default): YUV input is coded with
         Bloom inter-frames ('BFV2' container, which the reference's decompress_video rejects), anything
         else as keyframes; False: always the reference's all-keyframe 'BFVC' container, readable by the
-        reference; True: inter-frames for every colour space (lossless fallback to keyframes per frame)."""
+        reference; True: inter-frames for every colour space (lossless fallback to keyframes per frame).
+        mask_channels: "luma" (default) -- an inter-frame's mask is the luma residual mask, and a frame in which some pixel changed in
+        chroma but not in luma falls back to a keyframe; "all" -- the mask marks every pixel in which any sample changed (the all-channel
+        mask kernel), so every inter-frame the GPU can batch is coded as one.  Both write records today's decoder reads: a fresh default
+        compressor decompresses either container."""
+        if mask_channels not in ("luma", "all"):
+            raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
+        self.mask_channels = mask_channels
         self.inter_frames = inter_frames
         self.noise_tolerance = noise_tolerance
         self.keyframe_interval = max(1, int(keyframe_interval))
@@ -169,7 +177,7 @@ class ImprovedVideoCompressor:
     def inter(self):
         if self._inter is None:
             self._inter = VideoFrameCompressor(keyframe_interval=self.keyframe_interval, use_direct_yuv=True,
-                                               verbose=False, ctx=self._ctx)
+                                               verbose=False, ctx=self._ctx, mask_channels=self.mask_channels)
         return self._inter
 
     def _get_lanes(self, count):
@@ -202,11 +210,12 @@ class ImprovedVideoCompressor:
         if a.ndim == 3 and (a.shape[2] < 3 or a.shape[2] > 4):
             return None
         mask, values, _ = self.inter._calculate_frame_diff(a, b, threshold=0.0)
-        changed = (a != b)
-        if changed.ndim == 3:
-            changed = changed.any(axis=2)
-        if np.any(changed & (mask == 0)):        # chroma moved where luma did not: not representable
-            return None
+        if self.mask_channels != "all" or a.ndim == 2:     # (the all-channel mask marks every change by construction)
+            changed = (a != b)
+            if changed.ndim == 3:
+                changed = changed.any(axis=2)
+            if np.any(changed & (mask == 0)):    # chroma moved where luma did not: not representable
+                return None
         record, _ = self.inter._compress_frame_differences(mask, values)
         return struct.pack("<B", b.dtype.itemsize) + record
 
@@ -215,7 +224,7 @@ class ImprovedVideoCompressor:
         shard's halo frame), every other frame is coded against its predecessor -- except the frames named in `run_starts` (indices
         into seg), which are keyframes of the stream: they start a new run and the pair in front of them is not coded.  One upload,
         ONE rbf_encode_runs launch sequence for all the runs, ONE exact-size download of the packed record (rbf_pack_records), one
-        batched gather of the changed values (with the count of changes the luma mask cannot carry); zlib runs in `pool`.
+        batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.
         lane: the context and coders to use (default: lane 0); busy: list that receives the (start, end) time of this block's GPU work.
         Returns a list of futures / None per pair (None = needs a keyframe, or is one), or None when the block cannot be batched
         (mixed shapes or dtypes)."""
@@ -233,7 +242,8 @@ class ImprovedVideoCompressor:
         if lane is None:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
-        coder = lane.coder(W, H, len(seg), C, a.dtype.itemsize)
+        mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
+        coder = lane.coder(W, H, len(seg), C, a.dtype.itemsize, mc)
         coder.set_run_starts(list(run_starts))
         block = _as_block(data)
         t1 = time.perf_counter()
@@ -245,7 +255,10 @@ class ImprovedVideoCompressor:
         t3 = time.perf_counter()
         res = coder.results_packed()
         t4 = time.perf_counter()
-        values, uncovered = coder.gather_values(check_uncovered=True)
+        if mc == 1:
+            values, uncovered = coder.gather_values(check_uncovered=True)
+        else:
+            values, uncovered = coder.gather_values(check_uncovered=False), [0] * (len(seg) - 1)
         t5 = time.perf_counter()
         self._tm_add(stack=t1 - t0, upload=t2 - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
         if busy is not None:
