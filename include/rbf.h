@@ -394,6 +394,44 @@ int rbf_scatter_values(rbf_ctx *ctx, void *frame_dev, uint32_t width, uint32_t h
                        uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes, uint32_t sample_bytes,
                        uint32_t channels, const void *mask_dev, const void *values_dev);
 
+/* ---- sample codec: prediction residuals in a chunked Rice code (no reference counterpart) ---------- */
+/* The opt-in replacement of the record formats' zlib-9 for keyframes and changed values.  A SAMPLE STREAM codes N samples of B = 8 or 16
+ * bits: '<I' N | '<B' B | 3 zero bytes | k[C] | '<H' words[C] | zero padding to 4 bytes | the payload as '<I' words, C = ceil(N / 1024).
+ * Sample x with prediction pred: s = (x - pred) mod 2^B read as B-bit two's complement, u = 2s (s >= 0) or -2s - 1.  Chunk c codes samples
+ * [1024c, 1024c + 1024) from payload word words[0] + ... + words[c-1]; bit j of a chunk is bit (j & 31) of its word j >> 5; k[c] in [0, B] is
+ * the parameter of fewest bits (the smallest on a tie): k == B stores the B bits of u; otherwise q = u >> k < 16 is q one-bits, a zero-bit and
+ * the k low bits of u, and q >= 16 is 16 one-bits and the B bits of u (bits least significant first).  words[c] = ceil(chunk bits / 32).
+ * Frames are DENSE: height x width pixels of `channels` (1..4) interleaved samples, sample_bytes 1 or 2 (B = 8 * sample_bytes).
+ * Every entry checks its arguments -- B, channels, capacities, and a stream's header and table against its length -- before it launches
+ * anything: RBF_EINVAL with rbf_last_error().
+ *
+ * Keyframes: pred = the same channel of the pixel to the left; in column 0 of the pixel above; 0 for the first pixel.
+ *   rbf_rice_encode_intra  the streams of nframes frames (frame f at frames_dev + f * frame_stride_bytes), back to back at out_dev;
+ *                          stream_bytes (host, nframes) receives their sizes.  capacity_bytes must hold every stream stored raw:
+ *                          sum over streams of 4 * (ceil((8 + 3C) / 4) + sum over chunks ceil(chunk samples * B / 32)).  Blocks.
+ *   rbf_rice_decode_intra  one stream (HOST memory) of width * height * channels samples back into the dense frame at frame_dev.  Waits for the
+ *                          decode: a chunk whose codes do not end inside its declared words gives RBF_EINVAL and frame_dev is not written.
+ * Inter-frames: pred = the same sample of frame t-1, at the pixels whose mask bit is 1 (raster order, channels interleaved).
+ *   rbf_rice_encode_inter  pair f (f = 0..nframes-2: frame f+1 against frame f under mask f, rows as in rbf_gather_values_batch) gets the stream
+ *                          of its ones[f] * channels residuals; ones (host, nframes-1 entries) are the masks' set-bit counts (RBF_EINVAL after the
+ *                          run when a mask disagrees); a pair with ones[f] = 0 gets the 8-byte empty stream.  Layout, capacity and
+ *                          stream_bytes as for the keyframes.  Blocks.
+ *   rbf_rice_apply_inter   count streams (HOST memory, back to back, sizes in stream_bytes) against count masks: frames_dev holds count + 1
+ *                          dense frames, slot 0 = the frame in front of the run; slot j + 1 becomes slot j with pred + s written at mask j's '1'
+ *                          pixels.  Decodes every stream and checks every mask's count first: on any failure no frame slot is written. */
+int rbf_rice_encode_intra(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                          void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes);
+int rbf_rice_decode_intra(rbf_ctx *ctx, const void *stream, uint64_t stream_bytes, uint32_t width, uint32_t height,
+                          uint32_t channels, uint32_t sample_bytes, void *frame_dev);
+int rbf_rice_encode_inter(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                          const void *masks_dev, uint64_t mask_stride_bytes, const uint64_t *ones,
+                          void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes);
+int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stream_bytes, uint32_t count,
+                         uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                         const void *masks_dev, uint64_t mask_stride_bytes, void *frames_dev);
+
 #ifdef __cplusplus
 }
 #endif

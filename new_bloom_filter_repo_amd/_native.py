@@ -91,6 +91,11 @@ _PROTOS = {
     "rbf_filter_query_keys": (_int, [_vp, _vp, ctypes.POINTER(FilterParams), ctypes.POINTER(Seeds), _u32, _vp, _vp, _u64, _vp]),
     "rbf_gather_values": (_int, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
     "rbf_scatter_values": (_int, [_vp, _vp, _u32, _u32, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "rbf_rice_encode_intra": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64)]),
+    "rbf_rice_decode_intra": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _vp]),
+    "rbf_rice_encode_inter": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64,
+                                     ctypes.POINTER(_u64)]),
+    "rbf_rice_apply_inter": (_int, [_vp, _vp, ctypes.POINTER(_u64), _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
 }
 
 _lib = None

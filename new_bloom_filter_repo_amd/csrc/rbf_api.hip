@@ -6,6 +6,7 @@
 #include "rbf_kernels_u64.h"
 #include "rbf_kernels_noise.h"
 #include "rbf_kernels_pack.h"
+#include "rbf_kernels_rice.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -68,6 +69,13 @@ struct rbf_ctx {
     uint32_t *qimage = nullptr;      size_t qimage_cap = 0;       // probe image of the batch's filters (FP64 query kernel)
     int32_t *thr_tab = nullptr;      size_t thr_tab_cap = 0;      // per-pair thresholds of the mask kernels
     uint64_t *pack_base = nullptr;   size_t pack_base_cap = 0;    // running record size between pack chunks
+    // sample codec (rbf_kernels_rice.h)
+    uint16_t *rice_u = nullptr;      size_t rice_u_cap = 0;       // u values (encode) / s values (decode) of the call's streams
+    uint32_t *rice_kw = nullptr;     size_t rice_kw_cap = 0;      // per chunk: k | words << 8
+    uint64_t *rice_off = nullptr;    size_t rice_off_cap = 0;     // per chunk: payload word offset (+ the total), then per stream
+    void *rice_tab = nullptr;        size_t rice_tab_cap = 0;     // the call's stream / chunk table
+    void *rice_blob = nullptr;       size_t rice_blob_cap = 0;    // uploaded streams (decode)
+    uint32_t *rice_err = nullptr;    size_t rice_err_cap = 0;     // decode / apply error flag
     int force_generic = 0;           // tests: 1 = never use the LDS fast path
     int single_buffer = 0;           // tests: 1 = fast query path without filter double-buffering
     uint32_t mask_chunks = 0;        // tuning: temporal chunks of the GOP mask kernel (0 = auto)
@@ -293,6 +301,8 @@ int rbf_ctx_destroy(rbf_ctx *ctx)
     hash_table_release(ctx);
     if (ctx->thr_tab) (void)hipFree(ctx->thr_tab);
     if (ctx->pack_base) (void)hipFree(ctx->pack_base);
+    for (void *p : {(void *)ctx->rice_u, (void *)ctx->rice_kw, (void *)ctx->rice_off, ctx->rice_tab, ctx->rice_blob, (void *)ctx->rice_err})
+        if (p) (void)hipFree(p);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return RBF_OK;
@@ -1904,6 +1914,311 @@ int rbf_scatter_values(rbf_ctx *ctx, void *frame_dev, uint32_t width, uint32_t h
                        uint32_t channels, const void *mask_dev, const void *values_dev)
 {
     if (int r = values_common(ctx, frame_dev, width, height, row_pitch_bytes, pixel_stride_bytes, sample_bytes, channels, mask_dev, (void *)values_dev, nullptr, true)) return r;
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// sample codec (rbf_kernels_rice.h): prediction residuals in a chunked Rice code
+// ------------------------------------------------------------------------------------------
+static inline uint64_t rice_nchunks(uint64_t n) { return (n + RICE_CHUNK - 1) / RICE_CHUNK; }
+static inline uint64_t rice_header_words(uint64_t n) { return (8 + 3 * rice_nchunks(n) + 3) / 4; }
+
+// the longest stream of n samples of `bits` bits: every chunk stored raw
+static uint64_t rice_max_bytes(uint64_t n, uint32_t bits)
+{
+    const uint64_t full = n / RICE_CHUNK, tail = n % RICE_CHUNK;
+    return 4 * (rice_header_words(n) + full * (RICE_CHUNK * bits / 32) + (tail * bits + 31) / 32);
+}
+
+static int rice_check_frame(uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes)
+{
+    if (width == 0 || height == 0) return fail(RBF_EINVAL, "empty frame");
+    if (height > 65535) return fail(RBF_ERANGE, "at most 65535 rows, got %u", height);
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(RBF_EINVAL, "sample_bytes must be 1 or 2, got %u", sample_bytes);
+    if (channels == 0 || channels > 4) return fail(RBF_EINVAL, "channels must be 1..4, got %u", channels);
+    if ((uint64_t)width * height * channels > 0xFFFFFFFFull) return fail(RBF_ERANGE, "a stream holds at most 2^32-1 samples");
+    return RBF_OK;
+}
+
+struct RicePlan { std::vector<RiceStream> st; uint32_t nchunks = 0; uint64_t samples = 0; };
+
+// The stream table of an encode call (nstreams streams of n[s] samples, a sentinel behind them) and the capacity check.
+static int rice_plan(const uint64_t *n, uint32_t nstreams, uint32_t bits, uint64_t capacity_bytes, RicePlan *p)
+{
+    try { p->st.resize((size_t)nstreams + 1); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    uint64_t hdr = 0, chunks = 0, samples = 0, need = 0;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        if (n[s] > 0xFFFFFFFFull) return fail(RBF_ERANGE, "stream %u: %llu samples, a stream holds at most 2^32-1", s, (unsigned long long)n[s]);
+        p->st[s] = RiceStream{samples, hdr, (uint32_t)n[s], (uint32_t)chunks};
+        hdr += rice_header_words(n[s]);
+        chunks += rice_nchunks(n[s]);
+        samples += n[s];
+        need += rice_max_bytes(n[s], bits);
+    }
+    if (chunks > 0xFFFFFFFFull) return fail(RBF_ERANGE, "too many chunks in one call");
+    p->st[nstreams] = RiceStream{samples, hdr, 0, (uint32_t)chunks};
+    p->nchunks = (uint32_t)chunks;
+    p->samples = samples;
+    if (capacity_bytes < need)
+        return fail(RBF_EINVAL, "output capacity %llu bytes < %llu, the longest these streams can be", (unsigned long long)capacity_bytes, (unsigned long long)need);
+    return RBF_OK;
+}
+
+static int rice_stage(rbf_ctx *ctx, const RicePlan &p)
+{
+    if (int r = grow((void **)&ctx->rice_u, &ctx->rice_u_cap, (size_t)std::max<uint64_t>(p.samples, 1) * 2)) return r;
+    if (int r = grow((void **)&ctx->rice_kw, &ctx->rice_kw_cap, ((size_t)p.nchunks + 1) * 4)) return r;
+    if (int r = grow((void **)&ctx->rice_off, &ctx->rice_off_cap, ((size_t)p.nchunks + 1 + p.st.size()) * 8)) return r;
+    if (int r = grow(&ctx->rice_tab, &ctx->rice_tab_cap, p.st.size() * sizeof(RiceStream))) return r;
+    HIP_TRY(hipMemcpyAsync(ctx->rice_tab, p.st.data(), p.st.size() * sizeof(RiceStream), hipMemcpyHostToDevice, ctx->stream));
+    return RBF_OK;
+}
+
+// cost -> scan -> headers + payload words, then the stream sizes to the host (blocks)
+template <int B>
+static int rice_encode_streams(rbf_ctx *ctx, const RicePlan &p, void *out_dev, uint64_t *stream_bytes)
+{
+    const uint32_t nstreams = (uint32_t)p.st.size() - 1;
+    const RiceStream *st = (const RiceStream *)ctx->rice_tab;
+    uint64_t *goff = ctx->rice_off, *swords = ctx->rice_off + p.nchunks + 1;
+    const uint32_t bx = (p.nchunks + WG_WAVES - 1) / WG_WAVES;
+    if (p.nchunks)
+        hipLaunchKernelGGL(k_rice_cost<B>, dim3(bx), dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u, st, nstreams, p.nchunks, ctx->rice_kw);
+    hipLaunchKernelGGL(k_rice_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->rice_kw, p.nchunks, goff, st, nstreams, swords);
+    const uint64_t hw = p.st[nstreams].hdr_word;
+    hipLaunchKernelGGL(k_rice_headers, dim3((uint32_t)std::min<uint64_t>((hw + WG_THREADS - 1) / WG_THREADS, 4096)), dim3(WG_THREADS), 0, ctx->stream,
+                       ctx->rice_kw, st, nstreams, swords, (uint32_t)B, (uint32_t *)out_dev);
+    if (p.nchunks)
+        hipLaunchKernelGGL(k_rice_write<B>, dim3(bx), dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u, st, nstreams, p.nchunks, ctx->rice_kw, goff,
+                           (uint32_t *)out_dev);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> sw;
+    try { sw.resize(p.st.size()); } catch (...) { (void)hipStreamSynchronize(ctx->stream); return fail(RBF_ENOMEM, "out of host memory"); }
+    HIP_TRY(hipMemcpyAsync(sw.data(), swords, sw.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (uint32_t s = 0; s < nstreams; ++s)
+        stream_bytes[s] = 4 * ((p.st[s + 1].hdr_word + sw[s + 1]) - (p.st[s].hdr_word + sw[s]));
+    return RBF_OK;
+}
+
+static inline uint32_t rice_le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// Checks stream `idx` (len bytes at p) before anything is launched -- its bit width, the reserved and padding bytes, every k <= B, every
+// word count in 1 .. ceil(chunk samples * B / 32), the table against the stream's length -- and appends its chunks.  word0: the stream's
+// first word among the uploaded streams; out0: its first sample in the output.
+static int rice_parse(const uint8_t *p, uint64_t len, uint32_t idx, uint32_t bits, uint64_t word0, uint64_t out0,
+                      std::vector<RiceChunk> *chunks, uint64_t *n_out)
+{
+    if (len < 8 || len % 4) return fail(RBF_EINVAL, "sample stream %u: %llu bytes (a stream is >= 8 bytes, a multiple of 4)", idx, (unsigned long long)len);
+    const uint64_t n = rice_le32(p);
+    if (p[4] != bits) return fail(RBF_EINVAL, "sample stream %u codes %u-bit samples, the frame has %u", idx, (unsigned)p[4], bits);
+    if (p[5] | p[6] | p[7]) return fail(RBF_EINVAL, "sample stream %u: reserved header bytes are not zero", idx);
+    const uint64_t nch = rice_nchunks(n), hdr = 4 * rice_header_words(n);
+    if (hdr > len)
+        return fail(RBF_EINVAL, "sample stream %u: the table of %llu chunks runs past its %llu bytes", idx, (unsigned long long)nch, (unsigned long long)len);
+    for (uint64_t b = 8 + 3 * nch; b < hdr; ++b)
+        if (p[b]) return fail(RBF_EINVAL, "sample stream %u: padding bytes are not zero", idx);
+    uint64_t w = 0;
+    try {
+        for (uint64_t c = 0; c < nch; ++c) {
+            const uint32_t k = p[8 + c], words = (uint32_t)p[8 + nch + 2 * c] | (uint32_t)p[9 + nch + 2 * c] << 8;
+            const uint64_t nc = std::min<uint64_t>(RICE_CHUNK, n - c * RICE_CHUNK);
+            if (k > bits) return fail(RBF_EINVAL, "sample stream %u, chunk %llu: k = %u > %u", idx, (unsigned long long)c, k, bits);
+            if (words == 0 || words > (nc * bits + 31) / 32)
+                return fail(RBF_EINVAL, "sample stream %u, chunk %llu: %u words, a chunk of %llu samples has 1..%llu", idx, (unsigned long long)c, words,
+                            (unsigned long long)nc, (unsigned long long)((nc * bits + 31) / 32));
+            chunks->push_back(RiceChunk{word0 + hdr / 4 + w, out0 + c * RICE_CHUNK, words, (uint16_t)nc, (uint8_t)k, (uint8_t)bits});
+            w += words;
+        }
+    } catch (...) {
+        return fail(RBF_ENOMEM, "out of host memory");
+    }
+    if (hdr + 4 * w != len)
+        return fail(RBF_EINVAL, "sample stream %u: its table declares %llu bytes, the stream has %llu", idx, (unsigned long long)(hdr + 4 * w),
+                    (unsigned long long)len);
+    *n_out = n;
+    return RBF_OK;
+}
+
+// Uploads the streams and their chunk table, decodes every chunk into ctx->rice_u and waits: RBF_EINVAL when a chunk's codes do not end
+// inside its declared words.
+static int rice_decode(rbf_ctx *ctx, const void *streams, uint64_t nbytes, const std::vector<RiceChunk> &ch, uint64_t samples)
+{
+    if (int r = grow(&ctx->rice_blob, &ctx->rice_blob_cap, (size_t)std::max<uint64_t>(nbytes, 8))) return r;
+    if (int r = grow(&ctx->rice_tab, &ctx->rice_tab_cap, std::max<size_t>(ch.size(), 1) * sizeof(RiceChunk))) return r;
+    if (int r = grow((void **)&ctx->rice_u, &ctx->rice_u_cap, (size_t)std::max<uint64_t>(samples, 1) * 2)) return r;
+    if (int r = grow((void **)&ctx->rice_err, &ctx->rice_err_cap, 8)) return r;
+    HIP_TRY(hipMemcpyAsync(ctx->rice_blob, streams, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!ch.empty()) HIP_TRY(hipMemcpyAsync(ctx->rice_tab, ch.data(), ch.size() * sizeof(RiceChunk), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->rice_err, 0, 8, ctx->stream));
+    if (!ch.empty())
+        hipLaunchKernelGGL(k_rice_decode, dim3((uint32_t)((ch.size() + WG_WAVES - 1) / WG_WAVES)), dim3(WG_THREADS), 0, ctx->stream,
+                           (const uint32_t *)ctx->rice_blob, (const RiceChunk *)ctx->rice_tab, (uint32_t)ch.size(), ctx->rice_u, ctx->rice_err);
+    HIP_TRY(hipGetLastError());
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, ctx->rice_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (err) return fail(RBF_EINVAL, "corrupt sample stream: a chunk's codes do not end inside its declared words");
+    return RBF_OK;
+}
+
+extern "C" {
+
+int rbf_rice_encode_intra(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                          void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!frames_dev || !out_dev || !stream_bytes) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    if (nframes == 0 || nframes > 65535) return fail(RBF_EINVAL, "nframes must be 1..65535, got %u", nframes);
+    const uint64_t n = (uint64_t)width * height * channels;
+    if (frame_stride_bytes < n * sample_bytes || frame_stride_bytes % sample_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu cannot hold a dense frame of %llu bytes", (unsigned long long)frame_stride_bytes,
+                    (unsigned long long)(n * sample_bytes));
+    RicePlan p;
+    std::vector<uint64_t> ns;
+    try { ns.assign(nframes, n); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    if (int r = rice_plan(ns.data(), nframes, 8 * sample_bytes, capacity_bytes, &p)) return r;
+    if (int r = rice_stage(ctx, p)) return r;
+    const dim3 grid((uint32_t)(((uint64_t)width * channels + WG_THREADS - 1) / WG_THREADS), height, nframes);
+    if (sample_bytes == 1) {
+        hipLaunchKernelGGL(k_rice_intra_u<uint8_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes, width, channels, 8u,
+                           ctx->rice_u);
+        return rice_encode_streams<8>(ctx, p, out_dev, stream_bytes);
+    }
+    hipLaunchKernelGGL(k_rice_intra_u<uint16_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes, width, channels, 16u,
+                       ctx->rice_u);
+    return rice_encode_streams<16>(ctx, p, out_dev, stream_bytes);
+}
+
+int rbf_rice_encode_inter(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                          const void *masks_dev, uint64_t mask_stride_bytes, const uint64_t *ones,
+                          void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!frames_dev || !masks_dev || !ones || !out_dev || !stream_bytes) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    if (nframes < 2 || nframes > 65536) return fail(RBF_EINVAL, "nframes must be 2..65536, got %u", nframes);
+    const uint64_t npx = (uint64_t)width * height;
+    const uint32_t pairs = nframes - 1;
+    if (int r = check_frame_geometry(npx, pairs, mask_stride_bytes)) return r;
+    if (frame_stride_bytes < npx * channels * sample_bytes || frame_stride_bytes % sample_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu cannot hold a dense frame of %llu bytes", (unsigned long long)frame_stride_bytes,
+                    (unsigned long long)(npx * channels * sample_bytes));
+    std::vector<uint64_t> ns, got;
+    try { ns.resize(pairs); got.resize(pairs); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    for (uint32_t f = 0; f < pairs; ++f) {
+        if (ones[f] > npx) return fail(RBF_EINVAL, "pair %u: %llu changed pixels in a frame of %llu", f, (unsigned long long)ones[f], (unsigned long long)npx);
+        ns[f] = ones[f] * channels;
+    }
+    RicePlan p;
+    if (int r = rice_plan(ns.data(), pairs, 8 * sample_bytes, capacity_bytes, &p)) return r;
+    const uint64_t nseg = nseg_of(npx), nwords = (npx + 63) / 64;
+    if (int r = grow((void **)&ctx->seg_cnt, &ctx->seg_cnt_cap, (size_t)pairs * nseg * 4)) return r;
+    if (int r = grow((void **)&ctx->seg_off, &ctx->seg_off_cap, (size_t)pairs * nseg * 8)) return r;
+    if (int r = grow((void **)&ctx->pack_base, &ctx->pack_base_cap, ((size_t)pairs + 2) * 8)) return r;
+    if (int r = rice_stage(ctx, p)) return r;
+    hipLaunchKernelGGL(k_mask_segment_counts, dim3((uint32_t)((nseg + WG_WAVES - 1) / WG_WAVES), pairs), dim3(WG_THREADS), 0, ctx->stream,
+                       (const uint64_t *)masks_dev, mask_stride_bytes / 8, npx, ctx->seg_cnt, nseg);
+    hipLaunchKernelGGL(k_scan_segments, dim3(pairs), dim3(1024), 0, ctx->stream, ctx->seg_cnt, ctx->seg_off, nseg, ctx->pack_base, 1u);
+    const dim3 grid((uint32_t)((nwords + WG_THREADS - 1) / WG_THREADS), pairs);
+    int r;
+    if (sample_bytes == 1) {
+        hipLaunchKernelGGL(k_rice_inter_u<uint8_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes, npx, channels,
+                           (const uint64_t *)masks_dev, mask_stride_bytes / 8, ctx->seg_off, nseg, (const RiceStream *)ctx->rice_tab, 8u, ctx->rice_u);
+        r = rice_encode_streams<8>(ctx, p, out_dev, stream_bytes);
+    } else {
+        hipLaunchKernelGGL(k_rice_inter_u<uint16_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes, npx, channels,
+                           (const uint64_t *)masks_dev, mask_stride_bytes / 8, ctx->seg_off, nseg, (const RiceStream *)ctx->rice_tab, 16u, ctx->rice_u);
+        r = rice_encode_streams<16>(ctx, p, out_dev, stream_bytes);
+    }
+    if (r) return r;
+    // the counts the caller named must be the masks' (the producer never writes past them, so a wrong count gives a wrong stream)
+    HIP_TRY(hipMemcpyAsync(got.data(), ctx->pack_base, (size_t)pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (uint32_t f = 0; f < pairs; ++f)
+        if (got[f] != ones[f])
+            return fail(RBF_EINVAL, "pair %u: the mask marks %llu pixels, ones[%u] = %llu", f, (unsigned long long)got[f], f, (unsigned long long)ones[f]);
+    return RBF_OK;
+}
+
+int rbf_rice_decode_intra(rbf_ctx *ctx, const void *stream, uint64_t stream_bytes, uint32_t width, uint32_t height,
+                          uint32_t channels, uint32_t sample_bytes, void *frame_dev)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!stream || !frame_dev) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    const uint64_t want = (uint64_t)width * height * channels;
+    std::vector<RiceChunk> ch;
+    uint64_t n = 0;
+    if (int r = rice_parse((const uint8_t *)stream, stream_bytes, 0, 8 * sample_bytes, 0, 0, &ch, &n)) return r;
+    if (n != want)
+        return fail(RBF_EINVAL, "the stream carries %llu samples, a %ux%ux%u frame has %llu", (unsigned long long)n, width, height, channels,
+                    (unsigned long long)want);
+    if (int r = rice_decode(ctx, stream, stream_bytes, ch, n)) return r;
+    const dim3 grid((height + WG_WAVES - 1) / WG_WAVES);
+    if (sample_bytes == 1)
+        hipLaunchKernelGGL(k_rice_intra_rebuild<uint8_t>, grid, dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u, width, height, channels, 8u, (uint8_t *)frame_dev);
+    else
+        hipLaunchKernelGGL(k_rice_intra_rebuild<uint16_t>, grid, dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u, width, height, channels, 16u, (uint16_t *)frame_dev);
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stream_bytes, uint32_t count,
+                         uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                         const void *masks_dev, uint64_t mask_stride_bytes, void *frames_dev)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!streams || !stream_bytes || !masks_dev || !frames_dev) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    if (count == 0 || count > 65535) return fail(RBF_EINVAL, "count must be 1..65535, got %u", count);
+    const uint64_t npx = (uint64_t)width * height, fbytes = npx * channels * sample_bytes;
+    if (int r = check_frame_geometry(npx, count, mask_stride_bytes)) return r;
+    std::vector<RiceChunk> ch;
+    std::vector<uint64_t> n, first, got;
+    try { n.resize(count); first.resize(count); got.resize(count); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    uint64_t off = 0, samples = 0;
+    for (uint32_t j = 0; j < count; ++j) {
+        if (int r = rice_parse((const uint8_t *)streams + off, stream_bytes[j], j, 8 * sample_bytes, off / 4, samples, &ch, &n[j])) return r;
+        if (n[j] % channels)
+            return fail(RBF_EINVAL, "sample stream %u: %llu samples are not whole pixels of %u samples", j, (unsigned long long)n[j], channels);
+        first[j] = samples;
+        samples += n[j];
+        off += stream_bytes[j];
+    }
+    const uint64_t nseg = nseg_of(npx), nwords = (npx + 63) / 64;
+    if (int r = grow((void **)&ctx->seg_cnt, &ctx->seg_cnt_cap, (size_t)count * nseg * 4)) return r;
+    if (int r = grow((void **)&ctx->seg_off, &ctx->seg_off_cap, (size_t)count * nseg * 8)) return r;
+    if (int r = grow((void **)&ctx->pack_base, &ctx->pack_base_cap, ((size_t)count + 2) * 8)) return r;
+    hipLaunchKernelGGL(k_mask_segment_counts, dim3((uint32_t)((nseg + WG_WAVES - 1) / WG_WAVES), count), dim3(WG_THREADS), 0, ctx->stream,
+                       (const uint64_t *)masks_dev, mask_stride_bytes / 8, npx, ctx->seg_cnt, nseg);
+    hipLaunchKernelGGL(k_scan_segments, dim3(count), dim3(1024), 0, ctx->stream, ctx->seg_cnt, ctx->seg_off, nseg, ctx->pack_base, 1u);
+    if (int r = rice_decode(ctx, streams, off, ch, samples)) return r;              // (waits: the mask counts are in as well)
+    HIP_TRY(hipMemcpyAsync(got.data(), ctx->pack_base, (size_t)count * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (uint32_t j = 0; j < count; ++j)
+        if (got[j] * channels != n[j])
+            return fail(RBF_EINVAL, "sample stream %u carries %llu samples, its mask marks %llu pixels of %u samples", j, (unsigned long long)n[j],
+                        (unsigned long long)got[j], channels);
+    for (uint32_t j = 0; j < count; ++j) {                                          // every frame is checked: now the frames are written
+        uint8_t *dst = (uint8_t *)frames_dev + (uint64_t)(j + 1) * fbytes;
+        HIP_TRY(hipMemcpyAsync(dst, dst - fbytes, fbytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (!n[j]) continue;
+        const uint64_t *mask = (const uint64_t *)masks_dev + (uint64_t)j * (mask_stride_bytes / 8);
+        const dim3 grid((uint32_t)((nwords + WG_THREADS - 1) / WG_THREADS));
+        if (sample_bytes == 1)
+            hipLaunchKernelGGL(k_rice_inter_add<uint8_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (uint8_t *)dst, npx, channels, mask,
+                               ctx->seg_off + (uint64_t)j * nseg, ctx->rice_u + first[j], n[j] / channels, ctx->rice_err);
+        else
+            hipLaunchKernelGGL(k_rice_inter_add<uint16_t>, grid, dim3(WG_THREADS), 0, ctx->stream, (uint16_t *)dst, npx, channels, mask,
+                               ctx->seg_off + (uint64_t)j * nseg, ctx->rice_u + first[j], n[j] / channels, ctx->rice_err);
+    }
     HIP_TRY(hipGetLastError());
     return RBF_OK;
 }

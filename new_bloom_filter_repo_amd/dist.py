@@ -487,18 +487,19 @@ def gather_device_records(records, device, dst=0, group=None, max_records=None, 
     return out
 
 
-def encode_video_sharded(frames, first_index, nframes_total, keyframe_interval=30, ctx=None, dst=0, group=None, mask_channels="luma"):
+def encode_video_sharded(frames, first_index, nframes_total, keyframe_interval=30, ctx=None, dst=0, group=None, mask_channels="luma",
+                         sample_codec="zlib"):
     """Code this rank's shard and gather the container records on rank `dst`.
 
     frames: the frames this rank READS, i.e. global indices [halo_start(start), stop) where
     (start, stop) = shard_range(nframes_total, world, rank); first_index = halo_start(start).
-    mask_channels: "luma" or "all" (ImprovedVideoCompressor's keyword; every rank must pass the same).
+    mask_channels: "luma" or "all"; sample_codec: "zlib" or "rice" (ImprovedVideoCompressor's keywords; every rank must pass the same).
     Returns the container bytes on dst (ImprovedVideoCompressor._container), None elsewhere."""
     import torch.distributed as dist
     from .video_compressor import ImprovedVideoCompressor
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     start, stop = shard_range(nframes_total, world, rank)
-    comp = ImprovedVideoCompressor(keyframe_interval=keyframe_interval, ctx=ctx, mask_channels=mask_channels)
+    comp = ImprovedVideoCompressor(keyframe_interval=keyframe_interval, ctx=ctx, mask_channels=mask_channels, sample_codec=sample_codec)
     try:
         coded = comp.encode_range(frames, first_index, start, stop)      # blocks of two keyframe intervals over two GPU lanes; the lanes' memory is released inside
     finally:

@@ -290,6 +290,15 @@ class GopCoder:
             return vals
         return vals, self._uncov.numpy(self.ctx)[:8 * self.pairs].view(np.uint64).copy()
 
+    def rice_streams(self, ones, codec):
+        """The sample-codec streams of every pair (type-4 value fields, sample_codec.py): pair f's residuals of frame f+1 against frame f at
+        mask f's '1' pixels, all pairs in ONE rbf_rice_encode_inter launch sequence and one exact-size download.  ones: the masks' set-bit
+        counts (results_packed()'s); codec: the SampleCoder of this coder's context.  A skipped pair gets the empty stream."""
+        if self.frames is None:
+            raise ValueError("rice_streams needs the interleaved frames (keep_interleaved=True)")
+        return codec.encode_inter(self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W, self.H,
+                                  self.C, self.sb, self.masks.ptr, self.mask_stride, ones)
+
     def results_packed(self):
         """What results() returns, through ONE exact-size download: the rows are compacted into a record on the device (rbf_pack_records:
         header + the used bytes of every filter and witness, ~150 KB per 1080p frame instead of ~600 KB of padded rows), the record's

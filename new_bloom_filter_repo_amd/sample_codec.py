@@ -1,0 +1,216 @@
+"""The opt-in sample codec (ImprovedVideoCompressor(sample_codec="rice")): every stored sample is predicted, the prediction error is mapped
+to an unsigned value and written with a chunked Rice code, encoded and decoded on the GPU by csrc/rbf_kernels_rice.h through the C ABI's
+rbf_rice_* entries.  There is no CPU codec (tests/sample_codec_ref.py is the numpy reference the tests compare against).
+
+Format (normative, include/rbf.h has the bit layout):
+  stream    '<I' N | '<B' B | 3 zero bytes | k[C] | '<H' words[C] | zero pad to 4 bytes | payload ('<I' words), C = ceil(N / 1024)
+  mapping   s = (x - pred) mod 2^B read as a B-bit two's-complement value, u = 2s (s >= 0) or -2s - 1
+  code      per chunk of 1024 samples one k in [0, B]: k == B stores u; else q = u >> k < 16 is q one-bits, a zero-bit and the k low bits of
+            u, q >= 16 is 16 one-bits and the B bits of u
+
+Records of 'BFV2' containers (next to type 1 = zlib keyframe, 2 = inter-frame):
+  3 = keyframe     '<III' height, width, itemsize | '<B' channels (0 = a 2-D frame) | '<B' yuv (1 = decode to YUVFrame) | the stream of the
+                   H*W*C samples, predicted from the pixel to the left (column 0: the pixel above; the first pixel: 0), per channel
+  4 = inter-frame  type 2's bytes ('<B' itemsize + the "f64" wire record) with the stream of the pair's residuals against frame t-1 at the
+                   mask's pixels in the value field; value_count = its sample count
+"""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _native as nat
+from .frame_codec import YUVFrame, _PlaneDict, frame_data
+
+CHUNK = 1024
+KEY_RICE, INTER_RICE = 3, 4
+_KEY_HEAD = struct.Struct("<IIIBB")
+_PLANES = ("y_plane", "u_plane", "v_plane")
+
+
+def nchunks(n):
+    return (int(n) + CHUNK - 1) // CHUNK
+
+
+def header_bytes(n):
+    """Header, table and padding of a stream of n samples."""
+    return (8 + 3 * nchunks(n) + 3) // 4 * 4
+
+
+def max_stream_bytes(n, bits):
+    """The longest a stream of n samples can be: every chunk stored raw (k = B)."""
+    full, tail = divmod(int(n), CHUNK)
+    return header_bytes(n) + 4 * (full * (CHUNK * bits // 32) + (tail * bits + 31) // 32)
+
+
+def stream_info(buf):
+    """(N, B, the length its table declares) of a sample stream; ValueError when the table does not fit in buf."""
+    buf = memoryview(buf).cast("B")
+    if len(buf) < 8:
+        raise ValueError("sample stream shorter than its 8-byte header")
+    n, bits = struct.unpack_from("<IB", buf, 0)
+    c = nchunks(n)
+    if header_bytes(n) > len(buf):
+        raise ValueError("the table of a sample stream of %d chunks runs past its %d bytes" % (c, len(buf)))
+    words = np.frombuffer(buf[8 + c:8 + 3 * c], dtype="<u2")
+    return n, bits, header_bytes(n) + 4 * int(words.sum(dtype=np.int64))
+
+
+def key_format(frame):
+    """(channels byte, yuv byte) of the type-3 record that carries `frame`, or None when only a zlib keyframe can: samples other than
+    uint8 / uint16, more than 4 channels, or a yuv_info whose planes are not the frame's own channels."""
+    arr = frame_data(frame)
+    if arr.dtype not in (np.uint8, np.uint16) or arr.ndim not in (2, 3) or 0 in arr.shape:
+        return None
+    C = arr.shape[2] if arr.ndim == 3 else 1
+    if C > 4 or arr.shape[0] > 65535 or arr.shape[0] * arr.shape[1] * C >= 1 << 32:
+        return None
+    info = getattr(frame, "yuv_info", None)
+    if info is None:
+        return (0 if arr.ndim == 2 else C), 0
+    if not isinstance(frame, YUVFrame) or arr.ndim != 3 or C < 3 or info.get("format") != "YUV444":
+        return None
+    stored = {k: v for k, v in info.items() if k != "format"}          # (_PlaneDict: only the planes copied out so far)
+    if not isinstance(info, _PlaneDict) and set(stored) != set(_PLANES):
+        return None
+    for key, plane in stored.items():
+        if key not in _PLANES or not np.array_equal(np.asarray(plane), arr[..., _PLANES.index(key)]):
+            return None
+    return C, 1
+
+
+def key_record(frame, stream):
+    """The type-3 record of `frame` around its stream."""
+    arr = frame_data(frame)
+    channels, yuv = key_format(frame)
+    return _KEY_HEAD.pack(arr.shape[0], arr.shape[1], arr.dtype.itemsize, channels, yuv) + bytes(stream)
+
+
+def parse_key_record(rec):
+    """Fields of a type-3 record (height, width, itemsize, channels, yuv, stream); ValueError when they do not agree with each other."""
+    if len(rec) < _KEY_HEAD.size + 8:
+        raise ValueError("truncated keyframe record")
+    h, w, item, channels, yuv = _KEY_HEAD.unpack_from(rec, 0)
+    if item not in (1, 2) or channels > 4 or yuv > 1 or h == 0 or w == 0:
+        raise ValueError("keyframe record: itemsize %d, %d channels, yuv %d" % (item, channels, yuv))
+    stream = memoryview(rec)[_KEY_HEAD.size:]
+    n, bits, size = stream_info(stream)
+    if n != h * w * max(1, channels) or bits != 8 * item or size != len(stream):
+        raise ValueError("keyframe record: a stream of %d %d-bit samples in %d bytes for a %dx%dx%d frame of %d-byte samples"
+                         % (n, bits, len(stream), h, w, max(1, channels), item))
+    return {"height": h, "width": w, "itemsize": item, "channels": channels, "yuv": yuv, "stream": stream}
+
+
+def _split(raw, sizes):
+    out, off = [], 0
+    for s in sizes:
+        out.append(raw[off:off + int(s)])
+        off += int(s)
+    return out
+
+
+class SampleCoder:
+    """The sample codec on one library context: device buffers grown on demand (close() returns them)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._bufs = {}
+
+    def _buf(self, name, nbytes):
+        b = self._bufs.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._bufs[name] = self.ctx.alloc(max(8, int(nbytes)))
+        return b
+
+    def close(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+
+    def encode_frames(self, frames):
+        """Type-3 streams of same-shape frames: one upload per frame, ONE rbf_rice_encode_intra, one exact-size download."""
+        arrs = [frame_data(f) for f in frames]
+        a = arrs[0]
+        H, W = a.shape[:2]
+        C = a.shape[2] if a.ndim == 3 else 1
+        fb = self._buf("frames", a.nbytes * len(arrs))
+        for i, x in enumerate(arrs):
+            fb.upload(x, i * a.nbytes)
+        cap = len(arrs) * max_stream_bytes(H * W * C, 8 * a.dtype.itemsize)
+        ob = self._buf("streams", cap)
+        sizes = (ctypes.c_uint64 * len(arrs))()
+        nat.check(nat.lib().rbf_rice_encode_intra(self.ctx.handle, fb.ptr, a.nbytes, len(arrs), W, H, C, a.dtype.itemsize, ob.ptr, ob.nbytes, sizes))
+        return _split(ob.download(sum(sizes)).tobytes(), sizes)
+
+    def encode_inter(self, frames_ptr, frame_stride, nframes, width, height, channels, sample_bytes, masks_ptr, mask_stride, ones):
+        """Type-4 streams of the nframes-1 pairs of resident dense frames under their packed masks (rbf_rice_encode_inter): ONE launch
+        sequence, one exact-size download.  ones: the masks' set-bit counts."""
+        pairs = nframes - 1
+        cap = sum(max_stream_bytes(int(o) * channels, 8 * sample_bytes) for o in ones)
+        ob = self._buf("streams", cap)
+        sizes = (ctypes.c_uint64 * pairs)()
+        cnt = (ctypes.c_uint64 * pairs)(*[int(o) for o in ones])
+        nat.check(nat.lib().rbf_rice_encode_inter(self.ctx.handle, frames_ptr, frame_stride, nframes, width, height, channels, sample_bytes,
+                                                  masks_ptr, mask_stride, cnt, ob.ptr, ob.nbytes, sizes))
+        return _split(ob.download(sum(sizes)).tobytes(), sizes)
+
+    def encode_pair(self, prev, curr, mask_packed, ones):
+        """The type-4 stream of one pair (the frame-by-frame route's twin of GopCoder.rice_streams)."""
+        a, b = np.ascontiguousarray(frame_data(prev)), np.ascontiguousarray(frame_data(curr))
+        H, W = a.shape[:2]
+        C = a.shape[2] if a.ndim == 3 else 1
+        n = H * W
+        stride = nat.packed_stride(n)
+        fb = self._buf("pair", 2 * a.nbytes)
+        fb.upload(a, 0)
+        fb.upload(b, a.nbytes)
+        row = np.zeros(stride, dtype=np.uint8)
+        row[:(n + 7) // 8] = np.asarray(mask_packed, dtype=np.uint8)[:(n + 7) // 8]
+        mb = self._buf("pair_mask", stride).upload(row)
+        return self.encode_inter(fb.ptr, a.nbytes, 2, W, H, C, a.dtype.itemsize, mb.ptr, stride, [ones])[0]
+
+    def decode_frame(self, stream, height, width, channels, itemsize):
+        """A type-3 stream back to its frame: (H, W) for channels == 0, else (H, W, channels) (rbf_rice_decode_intra)."""
+        C = max(1, channels)
+        nbytes = height * width * C * itemsize
+        fb = self._buf("frame", nbytes)
+        src = np.frombuffer(stream, dtype=np.uint8)
+        nat.check(nat.lib().rbf_rice_decode_intra(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, fb.ptr))
+        out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
+        return out.reshape((height, width) if channels == 0 else (height, width, C))
+
+    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20):
+        """engine.apply_chain for type-4 records: frame t = frame t-1 plus the residuals of stream t at mask t's '1' pixels, rebuilt on the
+        device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  Returns the frames
+        as views of the downloaded chunk blocks."""
+        base = np.ascontiguousarray(base)
+        H, W = base.shape[:2]
+        C = base.shape[2] if base.ndim == 3 else 1
+        n = H * W
+        stride = nat.packed_stride(n)
+        fbytes = base.nbytes
+        total = len(masks_packed)
+        out = []
+        if total == 0:
+            return out
+        per = max(1, min(int(chunk_frames), total, int(chunk_bytes) // max(1, fbytes)))
+        fb = self._buf("chain", (per + 1) * fbytes)
+        mb = self._buf("masks", per * stride)
+        prev = base
+        for c0 in range(0, total, per):
+            cnt = min(per, total - c0)
+            rows = np.zeros((cnt, stride), dtype=np.uint8)
+            for j in range(cnt):
+                rows[j, :(n + 7) // 8] = np.asarray(masks_packed[c0 + j], dtype=np.uint8)[:(n + 7) // 8]
+            part = [bytes(s) for s in streams[c0:c0 + cnt]]
+            blob = np.frombuffer(b"".join(part), dtype=np.uint8)
+            sizes = (ctypes.c_uint64 * cnt)(*[len(s) for s in part])
+            fb.upload(prev, 0)
+            mb.upload(rows)
+            nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, base.dtype.itemsize, mb.ptr, stride, fb.ptr))
+            block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
+            out += [block[j] for j in range(cnt)]
+            prev = block[cnt - 1]
+        return out

@@ -11,7 +11,8 @@ mask of every pixel in which any sample changed instead, which covers every chan
 Container: all-keyframe streams are written exactly as the reference does -- 'BFVC' | <I frames |
 (<I len | record)* (:398-406) -- so either implementation reads them.  Streams with inter-frames use
 magic 'BFV2' and prefix every record with a type byte (1 = keyframe, 2 = inter-frame), following the
-type-byte precedent of VideoFrameCompressor.compress_frame (:1053).
+type-byte precedent of VideoFrameCompressor.compress_frame (:1053).  sample_codec="rice" writes types 3 and 4 instead: the same two
+roles with the GPU sample codec (sample_codec.py) in place of zlib-9.
 """
 import os
 import struct
@@ -24,8 +25,10 @@ import numpy as np
 
 from . import params as P
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
+from .sample_codec import INTER_RICE, KEY_RICE, key_format, key_record, parse_key_record, stream_info
 
 KEY, INTER = 1, 2
+KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
 _POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)   # numpy 1.x has no bitwise_count
 
 
@@ -60,6 +63,7 @@ class _Lane:
         self.ctx, self.owned = ctx, owned
         self.coders = {}
         self.engine = None
+        self.samples = None
 
     def coder(self, W, H, F, C, sb, mask_channels=1):
         from .gop import GopCoder
@@ -79,6 +83,12 @@ class _Lane:
             self.engine = BloomEngine(self.ctx)
         return self.engine
 
+    def sample_coder(self):
+        from .sample_codec import SampleCoder
+        if self.samples is None:
+            self.samples = SampleCoder(self.ctx)
+        return self.samples
+
     def release(self):
         for c in self.coders.values():
             c.close()
@@ -86,6 +96,9 @@ class _Lane:
         if self.engine is not None:
             self.engine.close()
             self.engine = None
+        if self.samples is not None:
+            self.samples.close()
+            self.samples = None
 
     def close(self):
         self.release()
@@ -110,8 +123,8 @@ class ImprovedVideoCompressor:
     def __init__(self, noise_tolerance=10.0, keyframe_interval=30, min_diff_threshold=3.0,
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
-                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma"):
-        """Reference signature (improved_video_compressor.py:318-327) plus six keyword-only extras:
+                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib"):
+        """Reference signature (improved_video_compressor.py:318-327) plus seven keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -124,9 +137,17 @@ class ImprovedVideoCompressor:
         mask_channels: "luma" (default) -- an inter-frame's mask is the luma residual mask, and a frame in which some pixel changed in
         chroma but not in luma falls back to a keyframe; "all" -- the mask marks every pixel in which any sample changed (the all-channel
         mask kernel), so every inter-frame the GPU can batch is coded as one.  Both write records today's decoder reads: a fresh default
-        compressor decompresses either container."""
+        compressor decompresses either container.
+        sample_codec: "zlib" (default) -- keyframes and changed values in zlib-9, the record formats' own; "rice" -- both through the GPU
+        sample codec (sample_codec.py: records 3 and 4, 'BFV2' only, so not with inter_frames=False); frames a type-3 record cannot carry
+        stay zlib keyframes.  decompress_video reads either with any settings."""
         if mask_channels not in ("luma", "all"):
             raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
+        if sample_codec not in ("zlib", "rice"):
+            raise ValueError("sample_codec must be 'zlib' or 'rice', got %r" % (sample_codec,))
+        if sample_codec == "rice" and inter_frames is False:
+            raise ValueError("sample_codec='rice' writes 'BFV2' records; inter_frames=False asks for 'BFVC', which holds zlib keyframes only")
+        self.sample_codec = sample_codec
         self.mask_channels = mask_channels
         self.inter_frames = inter_frames
         self.noise_tolerance = noise_tolerance
@@ -216,8 +237,22 @@ class ImprovedVideoCompressor:
                 changed = changed.any(axis=2)
             if np.any(changed & (mask == 0)):    # chroma moved where luma did not: not representable
                 return None
-        record, _ = self.inter._compress_frame_differences(mask, values)
+        if self.sample_codec == "rice":
+            record = self._inter_record_rice(mask, a, b)
+        else:
+            record, _ = self.inter._compress_frame_differences(mask, values)
         return struct.pack("<B", b.dtype.itemsize) + record
+
+    def _inter_record_rice(self, mask, a, b):
+        """_compress_frame_differences with the pair's sample stream (on lane 0) in the value field: the bytes _encode_block writes."""
+        flat = np.asarray(mask).reshape(-1)
+        bitmap, witness, p, n, _ = self.inter.bloom_compressor.compress(flat)
+        k, _l = self.inter.bloom_compressor._calculate_optimal_params(n, p)
+        ones = int(np.count_nonzero(flat))
+        stream = self._get_lanes(1)[0].sample_coder().encode_pair(a, b, np.packbits(flat.astype(np.uint8)), ones)
+        C = b.shape[2] if b.ndim == 3 else 1
+        return build_record(self.inter.wire_format, p, n, k, len(bitmap), np.packbits(bitmap).tobytes(), len(witness),
+                            np.packbits(np.array(witness, dtype=np.uint8)).tobytes(), ones * C, stream)
 
     def _encode_block(self, seg, pool, run_starts=(), lane=None, busy=None):
         """Inter-frame records of one block of consecutive frames in one pass over the GPU: seg[0] is only read (a keyframe, or a
@@ -255,10 +290,13 @@ class ImprovedVideoCompressor:
         t3 = time.perf_counter()
         res = coder.results_packed()
         t4 = time.perf_counter()
+        rice = self.sample_codec == "rice"
         if mc == 1:
             values, uncovered = coder.gather_values(check_uncovered=True)
         else:
-            values, uncovered = coder.gather_values(check_uncovered=False), [0] * (len(seg) - 1)
+            values, uncovered = None if rice else coder.gather_values(check_uncovered=False), [0] * (len(seg) - 1)
+        if rice:                                 # the value fields: every pair's residual stream in one launch sequence
+            values = coder.rice_streams([r["ones"] for r in res], lane.sample_coder())
         t5 = time.perf_counter()
         self._tm_add(stack=t1 - t0, upload=t2 - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
         if busy is not None:
@@ -279,10 +317,13 @@ class ImprovedVideoCompressor:
                 k, _l = P.optimal_params(n, p)
                 parts = (n, r["mask"], 0, b"")
             vals = values[f]
-
-            def job(p=p, k=k, parts=parts, vals=vals):
-                vz = zlib.compress(vals, level=9)
-                return struct.pack("<B", vals.dtype.itemsize) + build_record("f64", p, n, k, *parts, len(vals), vz)      # (VideoFrameCompressor's default wire format)
+            if rice:
+                def job(p=p, k=k, parts=parts, stream=vals, count=r["ones"] * C):
+                    return struct.pack("<B", a.dtype.itemsize) + build_record("f64", p, n, k, *parts, count, stream)
+            else:
+                def job(p=p, k=k, parts=parts, vals=vals):
+                    vz = zlib.compress(vals, level=9)
+                    return struct.pack("<B", vals.dtype.itemsize) + build_record("f64", p, n, k, *parts, len(vals), vz)      # (VideoFrameCompressor's default wire format)
             out.append(pool.submit(job))
         return out
 
@@ -299,11 +340,16 @@ class ImprovedVideoCompressor:
         self.last_timing = tm = {}
         t_all = time.perf_counter()
         busy = []
+        gpu_keys = set()                         # sample_codec="rice": keyframes coded as type-3 records on the lanes
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
 
             def key(t):
-                if t not in pending:
+                if t in pending or t in gpu_keys:
+                    return
+                if self.sample_codec == "rice" and key_format(frames[t - first_index]) is not None:
+                    gpu_keys.add(t)
+                else:
                     pending[t] = (KEY, self.compressor.compress_frame_jobs(frames[t - first_index], pool.submit))
             # the keyframes the rule fixes in advance go to the host threads FIRST: their zlib-9 (the longest single jobs, ~0.2 s for a 1080p
             # frame, plus its three planes) then runs under the GPU's blocks instead of behind the last one
@@ -355,21 +401,73 @@ class ImprovedVideoCompressor:
                     if inter is None:                                        # not batchable (or gop_batching=False): frame by frame
                         rec = self._encode_inter(seg[j - 1], seg[j])
                         if rec is not None:
-                            records[u] = (INTER, rec)
+                            records[u] = (INTER_RICE if self.sample_codec == "rice" else INTER, rec)
                             continue
                     if fut is not None:
                         pending[u] = (INTER, fut)
                     else:
                         key(u)
+            if gpu_keys:
+                t_key = time.perf_counter()
+                for u, rec in self._encode_keys_rice(frames, first_index, sorted(gpu_keys), busy).items():
+                    records[u] = (KEY_RICE, rec)
+                if release:
+                    self._release_lanes()
+                tm["gpu_phase"] += time.perf_counter() - t_key
             t_wait = time.perf_counter()
             for u, (ty, fut) in pending.items():
-                records[u] = (ty, fut() if ty == KEY else fut.result())
+                rec = fut() if ty == KEY else fut.result()
+                records[u] = (INTER_RICE if ty == INTER and self.sample_codec == "rice" else ty, rec)
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
         tm["total"] = time.perf_counter() - t_all
         tm["gpu_busy"] = _union_seconds(busy)                                # wall time during which at least one lane had a copy or a kernel in flight
         tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
         return [records[u] for u in range(start, stop)]
+
+    def _encode_keys_rice(self, frames, first_index, ts, busy):
+        """Type-3 records of the keyframes with global indices `ts`: batches of up to four frames of one shape, ONE rbf_rice_encode_intra
+        each, alternating over the GPU lanes like the blocks.  Returns {t: record}."""
+        import queue
+        batches = []
+        for t in ts:
+            a = frame_data(frames[t - first_index])
+            if batches and len(batches[-1][1]) < 4 and batches[-1][0] == (a.shape, a.dtype):
+                batches[-1][1].append(t)
+            else:
+                batches.append(((a.shape, a.dtype), [t]))
+        lanes = self._get_lanes(min(self.gpu_lanes, len(batches)))
+        free = queue.Queue()
+        for lane in lanes:
+            free.put(lane)
+
+        def run(b):
+            fs = [frames[t - first_index] for t in batches[b][1]]
+            lane = free.get()
+            try:
+                t0 = time.perf_counter()
+                streams = lane.sample_coder().encode_frames(fs)
+                busy.append((t0, time.perf_counter()))
+            finally:
+                free.put(lane)
+            return [key_record(f, s) for f, s in zip(fs, streams)]
+        if len(lanes) == 1:
+            outs = [run(b) for b in range(len(batches))]
+        else:
+            with ThreadPoolExecutor(len(lanes)) as gpu_pool:
+                outs = list(gpu_pool.map(run, range(len(batches))))
+        return {t: rec for (_, ts_b), recs in zip(batches, outs) for t, rec in zip(ts_b, recs)}
+
+    def _decode_key_rice(self, rec, lane=None, busy=None):
+        """A type-3 keyframe decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so."""
+        d = parse_key_record(rec)
+        if lane is None:
+            lane = self._get_lanes(1)[0]
+        t0 = time.perf_counter()
+        frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"])
+        if busy is not None:
+            busy.append((t0, time.perf_counter()))
+        return YUVFrame(frame) if d["yuv"] else frame
 
     def compress_video(self, frames, output_path=None, input_color_space="BGR"):
         """improved_video_compressor.py:358-450, same result dict.  Divergence: with inter-frames enabled
@@ -391,7 +489,7 @@ class ImprovedVideoCompressor:
         finally:
             self._release_lanes()                # (an exception in front of encode_range's own release)
         self.last_compressed_frames = records
-        keyframes = sum(1 for ty, _ in records if ty == KEY)
+        keyframes = sum(1 for ty, _ in records if ty in KEYS)
         if output_path:
             blob = self._container(records)
             os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
@@ -457,68 +555,85 @@ class ImprovedVideoCompressor:
         if not records:
             raise ValueError("No compressed frames provided")
         for ty, _ in records:
-            if ty not in (KEY, INTER):
+            if ty not in KEYS + INTERS:
                 raise ValueError(f"unknown record type {ty}")
-        if records[0][0] == INTER:
+        if records[0][0] in INTERS:
             raise ValueError("inter-frame without a preceding keyframe")
         self.last_timing = tm = {}
         busy = []
         # the keyframes are independent of everything else: inflate them on the host threads while the inter-frame runs go through the GPU
+        # (type-3 keyframes are decoded on the lanes: by the run that hangs off them, or by a job of their own)
         key_pool = ThreadPoolExecutor(self.num_threads)
         keys = {j: key_pool.submit(self.compressor.decompress_frame, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
+        gkeys = {}
         runs = []                                                            # (index of the keyframe in front, first record, end)
         i = 0
         while i < len(records):
-            if records[i][0] == KEY:
+            if records[i][0] in KEYS:
                 i += 1
                 continue
             j = i
-            while j < len(records) and records[j][0] == INTER:
+            while j < len(records) and records[j][0] in INTERS:
                 j += 1
             runs.append((i - 1, i, j))
             i = j
         decoded = {}
         try:
-            if self.gop_batching and runs:
+            bases = {k for k, _, _ in runs}
+            lone = [j for j, (ty, _) in enumerate(records) if ty == KEY_RICE and j not in bases]
+            if self.gop_batching and (runs or lone):
                 # every run hangs off its own keyframe, so the runs are independent: they alternate over the lanes, each on its own host
                 # thread -- the inflate and upload of run r+1 under the device-side rebuild and the download of run r
                 import queue
-                lanes = self._get_lanes(min(self.gpu_lanes, len(runs)))
+                jobs = [("run", r) for r in range(len(runs))] + [("key", j) for j in lone]
+                lanes = self._get_lanes(min(self.gpu_lanes, len(jobs)))
                 free = queue.Queue()
                 for lane in lanes:
                     free.put(lane)
 
-                def run_job(r):
-                    k, lo, hi = runs[r]
-                    base = keys[k].result()
+                def run_job(job):
+                    kind, x = job
+                    k, lo, hi = runs[x] if kind == "run" else (x, None, None)
+                    base = keys[k].result() if records[k][0] == KEY else None
                     lane = free.get()
                     try:
-                        return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy)
+                        if base is None:
+                            base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy)
+                        if kind == "key":
+                            return None
+                        return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=[ty for ty, _ in records[lo:hi]])
                     finally:
                         free.put(lane)
                 if len(lanes) == 1:
-                    outs = [run_job(r) for r in range(len(runs))]
+                    outs = [run_job(job) for job in jobs]
                 else:
                     with ThreadPoolExecutor(len(lanes)) as gpu_pool:
-                        outs = list(gpu_pool.map(run_job, range(len(runs))))
-                for (k, lo, hi), out in zip(runs, outs):
-                    decoded[lo] = out
+                        outs = list(gpu_pool.map(run_job, jobs))
+                for (kind, x), out in zip(jobs, outs):
+                    if kind == "run":
+                        decoded[runs[x][1]] = out
             frames = []
             i = 0
             while i < len(records):
                 ty, rec = records[i]
-                if ty == KEY:
-                    frames.append(keys[i].result())
+                if ty in KEYS:
+                    if ty == KEY:
+                        frames.append(keys[i].result())
+                    else:
+                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(rec))
                     i += 1
                     continue
                 j = i
-                while j < len(records) and records[j][0] == INTER:
+                while j < len(records) and records[j][0] in INTERS:
                     j += 1
                 if i in decoded:
                     frames += decoded[i]
                 else:
-                    for _, r in records[i:j]:
+                    for ty2, r in records[i:j]:
                         base = frames[-1]
+                        if ty2 == INTER_RICE:
+                            frames += self._decode_run(base, [r], types=[INTER_RICE])
+                            continue
                         dtype = np.uint8 if r[0] == 1 else np.uint16
                         mask, values = self.inter._decompress_frame_differences(r[1:], base.shape, dtype=dtype)
                         frames.append(self.inter._apply_frame_diff(base, mask, values))
@@ -536,29 +651,35 @@ class ImprovedVideoCompressor:
             print(f"Decompressed {len(frames)} frames in {time.time() - start:.2f} seconds")
         return frames
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None):
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None):
         """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
         ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
-        rebuilt in sequence on the device (engine.apply_chain).  lane: the context to use (default: lane 0);
-        pool: executor for the inflates (default: a temporary one)."""
+        rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
+        (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2)."""
         from .engine import apply_chain
         if lane is None:
             lane = self._get_lanes(1)[0]
+        types = [INTER] * len(recs) if types is None else list(types)
         t0 = time.perf_counter()
         base_arr = frame_data(base)
         n = base_arr.shape[0] * base_arr.shape[1]
         parsed = []
-        for r in recs:
+        for ty, r in zip(types, recs):
             d = parse_record("f64", r[1:])
             if d["n"] != n:
                 raise ValueError("inter-frame record of %d pixels after a frame of %d" % (d["n"], n))
             d["dtype"] = np.uint8 if r[0] == 1 else np.uint16
+            d["rice"] = ty == INTER_RICE
+            if d["rice"]:
+                cnt, bits, size = stream_info(d["values_z"])
+                if (cnt, bits, size) != (d["value_count"], 8 * base_arr.dtype.itemsize, len(d["values_z"])) or d["dtype"] != base_arr.dtype:
+                    raise ValueError("type-4 record: its sample stream (%d %d-bit samples, %d bytes) does not match the record" % (cnt, bits, size))
             parsed.append(d)
         inflate = lambda d: np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])[:d["value_count"]]
         own_pool = None
         if pool is None:
             pool = own_pool = ThreadPoolExecutor(self.num_threads)
-        val_jobs = [pool.submit(inflate, d) for d in parsed]                 # (run under the mask decode below)
+        val_jobs = [None if d["rice"] else pool.submit(inflate, d) for d in parsed]      # (run under the mask decode below)
         t1 = time.perf_counter()
         coded = [d for d in parsed if d["witness_bits"] > 0]
         if coded:
@@ -567,7 +688,7 @@ class ImprovedVideoCompressor:
             for d, m in zip(coded, masks):
                 d["mask"] = m
         t2 = time.perf_counter()
-        vals = [j.result() for j in val_jobs]
+        vals = [d["values_z"] if j is None else j.result() for j, d in zip(val_jobs, parsed)]
         if own_pool is not None:
             own_pool.shutdown()
         t3 = time.perf_counter()
@@ -575,12 +696,26 @@ class ImprovedVideoCompressor:
         ch = base_arr.shape[2] if base_arr.ndim == 3 else 1
         for i, (m, v) in enumerate(zip(masks, vals)):
             ones = _popcount(np.asarray(m, dtype=np.uint8)[:(n + 7) // 8])
+            if parsed[i]["rice"]:                # no reference behaviour to keep: a stream that does not fit its mask is an error
+                if parsed[i]["value_count"] != ones * ch:
+                    raise ValueError("type-4 record: %d residuals for a mask of %d pixels" % (parsed[i]["value_count"], ones))
+                continue
             if len(v) != ones * ch:              # same rule as _apply_frame_diff (:886-903)
                 if ch == 1:
                     raise ValueError("changed_values does not match the mask")
                 masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
         t4 = time.perf_counter()
-        out = apply_chain(lane.ctx, base_arr, masks, vals)
+        out, prev, i = [], base_arr, 0
+        while i < len(parsed):                   # stretches of one record type: values written (type 2) or residuals added (type 4)
+            j = i
+            while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
+                j += 1
+            if parsed[i]["rice"]:
+                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j])
+            else:
+                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j])
+            out += part
+            prev, i = part[-1], j
         t5 = time.perf_counter()
         self._tm_add(parse=t1 - t0, mask_decode=t2 - t1, inflate_wait=t3 - t2, check=t4 - t3, apply_chain=t5 - t4)
         if busy is not None:
