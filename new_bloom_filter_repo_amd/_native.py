@@ -190,6 +190,31 @@ class DeviceBuffer:
         return out.view(dtype)
 
 
+class BufferCache:
+    """Named device blocks of one context, grown on demand (close() returns them)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._bufs = {}
+
+    def get(self, name, nbytes):
+        """The block `name`, of at least nbytes: one that is too small is freed and allocated anew."""
+        b = self._bufs.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._bufs[name] = self.ctx.alloc(max(8, int(nbytes)))
+        return b
+
+    def __getitem__(self, name):
+        return self._bufs[name]
+
+    def close(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+
+
 class Context:
     """One HIP stream + scratch.  stream: an existing hipStream_t handle (int) or None."""
 
@@ -264,6 +289,21 @@ def default_context():
 def packed_stride(nbits):
     """Bytes of a packed bit vector buffer: whole 64-bit words."""
     return ((int(nbits) + 63) // 64) * 8
+
+
+def mask_rows(masks, n):
+    """Packed masks of n bits (each at least ceil(n/8) bytes long) as the rows the device reads: uint8 [count, packed_stride(n)], pad zero."""
+    nb = (int(n) + 7) // 8
+    rows = np.zeros((len(masks), packed_stride(n)), dtype=np.uint8)
+    for j, m in enumerate(masks):
+        rows[j, :nb] = np.asarray(m, dtype=np.uint8)[:nb]
+    return rows
+
+
+def frame_geometry(a):
+    """(H, W, C, sample bytes) of a frame array (H, W[, C])."""
+    H, W = a.shape[:2]
+    return H, W, a.shape[2] if a.ndim == 3 else 1, a.dtype.itemsize
 
 
 def params_array(plist):

@@ -1,0 +1,92 @@
+"""The video container, its record types and the layout of a stream: which frames are keyframes, where the encoder's blocks and the
+decoder's runs start and end (no numpy, no GPU).
+
+All-keyframe streams are written exactly as the reference does -- 'BFVC' | <I frames | (<I len | record)*
+(improved_video_compressor.py:398-406) -- so either implementation reads them.  Streams with any other record use magic 'BFV2' and prefix
+every record with a type byte, following the type-byte precedent of VideoFrameCompressor.compress_frame (:1053):
+  1 = keyframe (zlib, FixedVideoCompressor), 2 = inter-frame (Bloom record, values in zlib-9),
+  3, 4 = the same two roles with the GPU sample codec in place of zlib-9 (sample_codec.py has their layout).
+"""
+import struct
+
+KEY, INTER, KEY_RICE, INTER_RICE = 1, 2, 3, 4
+KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
+
+
+def write(records):
+    """The container bytes of [(type, record)]."""
+    all_key = all(ty == KEY for ty, _ in records)
+    out = [b"BFVC" if all_key else b"BFV2", struct.pack("<I", len(records))]
+    for ty, rec in records:
+        body = rec if all_key else struct.pack("<B", ty) + rec
+        out += [struct.pack("<I", len(body)), body]
+    return b"".join(out)
+
+
+def size(records):
+    """len(write(records)) without building it."""
+    extra = 0 if all(ty == KEY for ty, _ in records) else 1
+    return 8 + sum(4 + extra + len(rec) for _, rec in records)
+
+
+def parse(blob):
+    """[(type, record)] of a container."""
+    magic = blob[:4]
+    if magic not in (b"BFVC", b"BFV2"):
+        raise ValueError(f"Invalid file format: {magic}")
+    (count,) = struct.unpack_from("<I", blob, 4)
+    off, records = 8, []
+    for _ in range(count):
+        (length,) = struct.unpack_from("<I", blob, off)
+        body = blob[off + 4: off + 4 + length]
+        off += 4 + length
+        records.append((KEY, body) if magic == b"BFVC" else (body[0], body[1:]))
+    return records
+
+
+def check_types(types):
+    """ValueError unless every type is known and the stream starts with a keyframe."""
+    for ty in types:
+        if ty not in KEYS + INTERS:
+            raise ValueError(f"unknown record type {ty}")
+    if types and types[0] in INTERS:
+        raise ValueError("inter-frame without a preceding keyframe")
+
+
+def inter_runs(types):
+    """The maximal runs of inter-frame records of a checked stream: [(index of the keyframe in front, first record, end)]."""
+    runs, i = [], 0
+    while i < len(types):
+        if types[i] in KEYS:
+            i += 1
+            continue
+        j = i
+        while j < len(types) and types[j] in INTERS:
+            j += 1
+        runs.append((i - 1, i, j))
+        i = j
+    return runs
+
+
+def is_keyframe(t, first_index, keyframe_interval, inter_frames=True):
+    """The keyframe rule for global frame t of a call whose first frame is global frame first_index: t % keyframe_interval == 0, or no
+    inter-frames at all, or the frame's predecessor is not among the frames handed in."""
+    return not inter_frames or t % keyframe_interval == 0 or t - 1 < first_index
+
+
+def plan_range(first_index, start, stop, keyframe_interval, block_frames, inter_frames):
+    """What encode_range does with the frames [start, stop) of a call whose frames begin at global index first_index: (fixed_keys, blocks).
+    fixed_keys: the frames the rule makes keyframes, ascending.  blocks: [(first frame read, end, run starts)] -- a block reads the frames
+    lo .. end-1 (at most block_frames, several GOPs), codes every frame but the first against its predecessor, and its run starts (indices
+    into the block) are the keyframes inside it, which start a new run."""
+    fixed = [t for t in range(start, stop) if is_keyframe(t, first_index, keyframe_interval, inter_frames)]
+    blocks = []
+    t = start
+    while t < stop:
+        if is_keyframe(t, first_index, keyframe_interval, inter_frames):
+            t += 1
+            continue
+        end = min(stop, t - 1 + block_frames)                            # the block reads frames t-1 .. end-1
+        blocks.append((t - 1, end, [u - (t - 1) for u in range(t, end) if is_keyframe(u, first_index, keyframe_interval)]))      # keyframes inside the block: new runs
+        t = end
+    return fixed, blocks

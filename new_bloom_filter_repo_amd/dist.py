@@ -494,8 +494,9 @@ def encode_video_sharded(frames, first_index, nframes_total, keyframe_interval=3
     frames: the frames this rank READS, i.e. global indices [halo_start(start), stop) where
     (start, stop) = shard_range(nframes_total, world, rank); first_index = halo_start(start).
     mask_channels: "luma" or "all"; sample_codec: "zlib" or "rice" (ImprovedVideoCompressor's keywords; every rank must pass the same).
-    Returns the container bytes on dst (ImprovedVideoCompressor._container), None elsewhere."""
+    Returns the container bytes on dst (container.write), None elsewhere."""
     import torch.distributed as dist
+    from . import container
     from .video_compressor import ImprovedVideoCompressor
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     start, stop = shard_range(nframes_total, world, rank)
@@ -509,4 +510,4 @@ def encode_video_sharded(frames, first_index, nframes_total, keyframe_interval=3
     if merged is None:
         return None
     assert [t for t, _, _ in merged] == list(range(nframes_total)), "missing frames in the gather"
-    return ImprovedVideoCompressor._container([(ty, rec) for _, ty, rec in merged])
+    return container.write([(ty, rec) for _, ty, rec in merged])

@@ -15,22 +15,11 @@ from . import params as P
 class BloomEngine:
     def __init__(self, ctx=None):
         self.ctx = ctx or nat.default_context()
-        self._bufs = {}
-
-    # ------------------------------------------------------------------ buffers
-    def _buf(self, name, nbytes):
-        b = self._bufs.get(name)
-        if b is None or b.nbytes < nbytes:
-            if b is not None:
-                b.free()
-            b = self.ctx.alloc(max(int(nbytes), 8))
-            self._bufs[name] = b
-        return b
+        self.bufs = nat.BufferCache(self.ctx)
+        self._buf = self.bufs.get
 
     def close(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
+        self.bufs.close()
 
     def __enter__(self):
         return self
@@ -162,10 +151,7 @@ class BloomEngine:
         masks_packed = np.atleast_2d(np.asarray(masks_packed, dtype=np.uint8))
         F = masks_packed.shape[0]
         stride = nat.packed_stride(n)
-        rows = np.zeros((F, stride), dtype=np.uint8)
-        nb = (n + 7) // 8
-        rows[:, :nb] = masks_packed[:, :nb]
-        self._buf("masks", F * stride).upload(rows)
+        self._buf("masks", F * stride).upload(nat.mask_rows(masks_packed, n))
         self.n, self.mask_stride = n, stride
         return F
 
@@ -177,7 +163,7 @@ class BloomEngine:
         stride = nat.packed_stride(n)
         fstride = max(nat.packed_stride(p[0]) for p in plist)
         wstride = nat.packed_stride(n)
-        mb = self._bufs["masks"]
+        mb = self.bufs["masks"]
         fb = self._buf("filters", F * fstride)
         wb = self._buf("witness", F * wstride)
         sb = self._buf("stats", F * nat.STATS_PER_FRAME * 8)
@@ -343,13 +329,9 @@ class DeviceFilter:
 def gather_values(ctx, frame, mask_packed):
     """Changed-pixel values of `frame` (H, W[, C]) at the mask's '1' pixels, raster order (A2)."""
     frame = np.ascontiguousarray(frame)
-    H, W = frame.shape[:2]
-    C = frame.shape[2] if frame.ndim == 3 else 1
-    sb = frame.dtype.itemsize
-    n = H * W
+    H, W, C, sb = nat.frame_geometry(frame)
     fb = ctx.alloc(frame.nbytes).upload(frame)
-    row = np.zeros(nat.packed_stride(n), dtype=np.uint8)
-    row[:(n + 7) // 8] = np.asarray(mask_packed, dtype=np.uint8)[:(n + 7) // 8]
+    row = nat.mask_rows([mask_packed], H * W)
     mb = ctx.alloc(row.nbytes).upload(row)
     vb = ctx.alloc(max(frame.nbytes, 8))
     cb = ctx.alloc(8)
@@ -361,17 +343,15 @@ def gather_values(ctx, frame, mask_packed):
     return vals
 
 
-def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20):
-    """A8 for a run of inter-frames: frame t = frame t-1 with `values_list[t]` written at mask t's '1' pixels
-    (improved_video_compressor.py:849-909).  The run is rebuilt ON THE DEVICE in chunks of at most `chunk_frames` frames and `chunk_bytes`
-    bytes (1080p YUV444: 41 frames; an 8K 16-bit frame: one at a time -- device block and host block stay bounded whatever the frame
-    size): one upload of the chunk's masks, one of its values, then per frame a device-to-device copy of its predecessor and one
-    scatter, no host round trip in between; the chunk's frames come back in ONE download.
-    Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
-    base = np.ascontiguousarray(base)
-    H, W = base.shape[:2]
-    C = base.shape[2] if base.ndim == 3 else 1
-    sb = base.dtype.itemsize
+def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild):
+    """The chunked device-side rebuild of a run of inter-frames after `base` that both record types share (apply_chain below, SampleCoder.
+    apply_chain).  The run is rebuilt in chunks of at most `chunk_frames` frames and `chunk_bytes` bytes (1080p YUV444: 41 frames; an 8K
+    16-bit frame: one at a time -- device block and host block stay bounded whatever the frame size): one upload of the chunk's predecessor
+    into slot 0 of a block of frames `fb`, one of its masks as padded rows `mb`, then rebuild(c0, cnt, fb, mb) has the device write frames
+    c0 .. c0+cnt-1 of the run into slots 1 .. cnt, no host round trip in between; the chunk's frames come back in ONE download.
+    alloc(name, nbytes): the device blocks.  Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them
+    alive keeps its whole chunk alive."""
+    H, W, _, _ = nat.frame_geometry(base)
     n = H * W
     stride = nat.packed_stride(n)
     fbytes = base.nbytes
@@ -379,38 +359,59 @@ def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_byt
     out = []
     if total == 0:
         return out
-    L = nat.lib()
     per = max(1, min(int(chunk_frames), total, int(chunk_bytes) // max(1, fbytes)))
-    fb = ctx.alloc((per + 1) * fbytes)                            # slot 0: the predecessor of the chunk's first frame
-    mb = ctx.alloc(per * stride)
-    vcap = 8
-    for c0 in range(0, total, per):
-        vcap = max(vcap, sum(np.asarray(v).nbytes for v in values_list[c0:c0 + per]))
-    vb = ctx.alloc(vcap)
+    fb = alloc("chain", (per + 1) * fbytes)                       # slot 0: the predecessor of the chunk's first frame
+    mb = alloc("masks", per * stride)
     prev = base
     for c0 in range(0, total, per):
         cnt = min(per, total - c0)
-        rows = np.zeros((cnt, stride), dtype=np.uint8)
+        fb.upload(prev, 0)
+        mb.upload(nat.mask_rows(masks_packed[c0:c0 + cnt], n))
+        rebuild(c0, cnt, fb, mb)
+        block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
+        out += [block[j] for j in range(cnt)]
+        prev = block[cnt - 1]
+    return out
+
+
+def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20):
+    """A8 for a run of inter-frames: frame t = frame t-1 with `values_list[t]` written at mask t's '1' pixels
+    (improved_video_compressor.py:849-909), rebuilt ON THE DEVICE in chunks (rebuild_chain): one upload of the chunk's values, then per
+    frame a device-to-device copy of its predecessor and one scatter.
+    Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
+    base = np.ascontiguousarray(base)
+    H, W, C, sb = nat.frame_geometry(base)
+    stride = nat.packed_stride(H * W)
+    fbytes = base.nbytes
+    L = nat.lib()
+    bufs = []
+
+    def alloc(name, nbytes):
+        bufs.append(ctx.alloc(nbytes))
+        return bufs[-1]
+
+    def rebuild(c0, cnt, fb, mb):
+        if len(bufs) == 2:                                        # the first chunk is a full one: one value block for the largest chunk
+            vcap = 8
+            for c in range(0, len(masks_packed), cnt):
+                vcap = max(vcap, sum(np.asarray(v).nbytes for v in values_list[c:c + cnt]))
+            alloc("values", vcap)
+        vb = bufs[2]
         vals, offs = [], []
         off = 0
         for j in range(cnt):
-            rows[j, :(n + 7) // 8] = np.asarray(masks_packed[c0 + j], dtype=np.uint8)[:(n + 7) // 8]
             v = np.ascontiguousarray(values_list[c0 + j], dtype=base.dtype).reshape(-1)
             offs.append(off)
             off += v.nbytes
             vals.append(v)
-        fb.upload(prev, 0)
-        mb.upload(rows)
         if off:
             vb.upload(np.concatenate(vals))
         for j in range(cnt):
             dst = fb.ptr + (j + 1) * fbytes
             nat.check(L.rbf_memcpy_d2d(ctx.handle, dst, fb.ptr + j * fbytes, fbytes))
             nat.check(L.rbf_scatter_values(ctx.handle, dst, W, H, W * C * sb, C * sb, sb, C, mb.ptr + j * stride, vb.ptr + offs[j]))
-        block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
-        out += [block[j] for j in range(cnt)]
-        prev = block[cnt - 1]
-    for b in (fb, mb, vb):
+    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild)
+    for b in bufs:
         b.free()
     return out
 
@@ -418,14 +419,10 @@ def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_byt
 def scatter_values(ctx, frame, mask_packed, values):
     """Copy of `frame` with `values` written at the mask's '1' pixels, raster order (A8)."""
     frame = np.ascontiguousarray(frame)
-    H, W = frame.shape[:2]
-    C = frame.shape[2] if frame.ndim == 3 else 1
-    sb = frame.dtype.itemsize
-    n = H * W
+    H, W, C, sb = nat.frame_geometry(frame)
     values = np.ascontiguousarray(values, dtype=frame.dtype).reshape(-1)
     fb = ctx.alloc(frame.nbytes).upload(frame)
-    row = np.zeros(nat.packed_stride(n), dtype=np.uint8)
-    row[:(n + 7) // 8] = np.asarray(mask_packed, dtype=np.uint8)[:(n + 7) // 8]
+    row = nat.mask_rows([mask_packed], H * W)
     mb = ctx.alloc(row.nbytes).upload(row)
     vb = ctx.alloc(max(values.nbytes, 8))
     if values.nbytes:

@@ -20,10 +20,11 @@ import struct
 import numpy as np
 
 from . import _native as nat
+from .container import INTER_RICE, KEY_RICE  # noqa: F401  (the record types this module's streams travel in)
+from .engine import rebuild_chain
 from .frame_codec import YUVFrame, _PlaneDict, frame_data
 
 CHUNK = 1024
-KEY_RICE, INTER_RICE = 3, 4
 _KEY_HEAD = struct.Struct("<IIIBB")
 _PLANES = ("y_plane", "u_plane", "v_plane")
 
@@ -62,8 +63,8 @@ def key_format(frame):
     arr = frame_data(frame)
     if arr.dtype not in (np.uint8, np.uint16) or arr.ndim not in (2, 3) or 0 in arr.shape:
         return None
-    C = arr.shape[2] if arr.ndim == 3 else 1
-    if C > 4 or arr.shape[0] > 65535 or arr.shape[0] * arr.shape[1] * C >= 1 << 32:
+    H, W, C, _ = nat.frame_geometry(arr)
+    if C > 4 or H > 65535 or H * W * C >= 1 << 32:
         return None
     info = getattr(frame, "yuv_info", None)
     if info is None:
@@ -114,27 +115,17 @@ class SampleCoder:
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self._bufs = {}
-
-    def _buf(self, name, nbytes):
-        b = self._bufs.get(name)
-        if b is None or b.nbytes < nbytes:
-            if b is not None:
-                b.free()
-            b = self._bufs[name] = self.ctx.alloc(max(8, int(nbytes)))
-        return b
+        self.bufs = nat.BufferCache(ctx)
+        self._buf = self.bufs.get
 
     def close(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
+        self.bufs.close()
 
     def encode_frames(self, frames):
         """Type-3 streams of same-shape frames: one upload per frame, ONE rbf_rice_encode_intra, one exact-size download."""
         arrs = [frame_data(f) for f in frames]
         a = arrs[0]
-        H, W = a.shape[:2]
-        C = a.shape[2] if a.ndim == 3 else 1
+        H, W, C, _ = nat.frame_geometry(a)
         fb = self._buf("frames", a.nbytes * len(arrs))
         for i, x in enumerate(arrs):
             fb.upload(x, i * a.nbytes)
@@ -159,17 +150,13 @@ class SampleCoder:
     def encode_pair(self, prev, curr, mask_packed, ones):
         """The type-4 stream of one pair (the frame-by-frame route's twin of GopCoder.rice_streams)."""
         a, b = np.ascontiguousarray(frame_data(prev)), np.ascontiguousarray(frame_data(curr))
-        H, W = a.shape[:2]
-        C = a.shape[2] if a.ndim == 3 else 1
-        n = H * W
-        stride = nat.packed_stride(n)
+        H, W, C, sb = nat.frame_geometry(a)
+        stride = nat.packed_stride(H * W)
         fb = self._buf("pair", 2 * a.nbytes)
         fb.upload(a, 0)
         fb.upload(b, a.nbytes)
-        row = np.zeros(stride, dtype=np.uint8)
-        row[:(n + 7) // 8] = np.asarray(mask_packed, dtype=np.uint8)[:(n + 7) // 8]
-        mb = self._buf("pair_mask", stride).upload(row)
-        return self.encode_inter(fb.ptr, a.nbytes, 2, W, H, C, a.dtype.itemsize, mb.ptr, stride, [ones])[0]
+        mb = self._buf("pair_mask", stride).upload(nat.mask_rows([mask_packed], H * W))
+        return self.encode_inter(fb.ptr, a.nbytes, 2, W, H, C, sb, mb.ptr, stride, [ones])[0]
 
     def decode_frame(self, stream, height, width, channels, itemsize):
         """A type-3 stream back to its frame: (H, W) for channels == 0, else (H, W, channels) (rbf_rice_decode_intra)."""
@@ -186,31 +173,12 @@ class SampleCoder:
         device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  Returns the frames
         as views of the downloaded chunk blocks."""
         base = np.ascontiguousarray(base)
-        H, W = base.shape[:2]
-        C = base.shape[2] if base.ndim == 3 else 1
-        n = H * W
-        stride = nat.packed_stride(n)
-        fbytes = base.nbytes
-        total = len(masks_packed)
-        out = []
-        if total == 0:
-            return out
-        per = max(1, min(int(chunk_frames), total, int(chunk_bytes) // max(1, fbytes)))
-        fb = self._buf("chain", (per + 1) * fbytes)
-        mb = self._buf("masks", per * stride)
-        prev = base
-        for c0 in range(0, total, per):
-            cnt = min(per, total - c0)
-            rows = np.zeros((cnt, stride), dtype=np.uint8)
-            for j in range(cnt):
-                rows[j, :(n + 7) // 8] = np.asarray(masks_packed[c0 + j], dtype=np.uint8)[:(n + 7) // 8]
+        H, W, C, sb = nat.frame_geometry(base)
+        stride = nat.packed_stride(H * W)
+
+        def rebuild(c0, cnt, fb, mb):
             part = [bytes(s) for s in streams[c0:c0 + cnt]]
             blob = np.frombuffer(b"".join(part), dtype=np.uint8)
             sizes = (ctypes.c_uint64 * cnt)(*[len(s) for s in part])
-            fb.upload(prev, 0)
-            mb.upload(rows)
-            nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, base.dtype.itemsize, mb.ptr, stride, fb.ptr))
-            block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
-            out += [block[j] for j in range(cnt)]
-            prev = block[cnt - 1]
-        return out
+            nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, sb, mb.ptr, stride, fb.ptr))
+        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild)

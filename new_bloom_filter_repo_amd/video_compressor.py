@@ -8,13 +8,12 @@ only emitted when applying its record to frame t-1 reproduces frame t bit for bi
 threshold 0 must cover every changed pixel); otherwise that frame falls back to a keyframe.  mask_channels="all" codes the
 mask of every pixel in which any sample changed instead, which covers every change by construction.
 
-Container: all-keyframe streams are written exactly as the reference does -- 'BFVC' | <I frames |
-(<I len | record)* (:398-406) -- so either implementation reads them.  Streams with inter-frames use
-magic 'BFV2' and prefix every record with a type byte (1 = keyframe, 2 = inter-frame), following the
-type-byte precedent of VideoFrameCompressor.compress_frame (:1053).  sample_codec="rice" writes types 3 and 4 instead: the same two
-roles with the GPU sample codec (sample_codec.py) in place of zlib-9.
+Container and record types: container.py.  sample_codec="rice" writes types 3 and 4 instead of 1 and 2: the same two roles with the GPU
+sample codec (sample_codec.py) in place of zlib-9.
 """
+import contextlib
 import os
+import queue
 import struct
 import threading
 import time
@@ -23,12 +22,13 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from . import container
 from . import params as P
+from ._native import frame_geometry
+from .container import INTER, INTER_RICE, KEY, KEY_RICE, KEYS, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
-from .sample_codec import INTER_RICE, KEY_RICE, key_format, key_record, parse_key_record, stream_info
+from .sample_codec import key_format, key_record, parse_key_record, stream_info
 
-KEY, INTER = 1, 2
-KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
 _POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)   # numpy 1.x has no bitwise_count
 
 
@@ -106,6 +106,33 @@ class _Lane:
             self.ctx.close()
 
 
+class _LanePool:
+    """The jobs of one call spread over its lanes: `free` holds the lanes no job is using."""
+
+    def __init__(self, lanes):
+        self.lanes = list(lanes)
+        self.free = queue.Queue()
+        for lane in self.lanes:
+            self.free.put(lane)
+
+    @contextlib.contextmanager
+    def take(self):
+        """`with pool.take() as lane:` -- waits for a free lane and returns it whatever happens inside."""
+        lane = self.free.get()
+        try:
+            yield lane
+        finally:
+            self.free.put(lane)
+
+    def map(self, jobs, fn):
+        """[fn(job, self.take) for job in jobs]: fn holds a lane for the part of its work that needs one.  One lane: the jobs run in order on
+        the calling thread; more: on len(lanes) threads, started in order.  An exception in a job reaches the caller."""
+        if len(self.lanes) == 1:
+            return [fn(job, self.take) for job in jobs]
+        with ThreadPoolExecutor(len(self.lanes)) as gpu_pool:
+            return list(gpu_pool.map(lambda job: fn(job, self.take), jobs))
+
+
 def _union_seconds(intervals):
     """Total length of the union of (t0, t1) intervals."""
     total, end = 0.0, None
@@ -117,6 +144,13 @@ def _union_seconds(intervals):
             total += t1 - end
             end = t1
     return total
+
+
+def _close_timing(tm, t_all, busy):
+    """The totals of a last_timing dict: `busy` holds the (start, end) times of the lanes' GPU work since t_all."""
+    tm["total"] = time.perf_counter() - t_all
+    tm["gpu_busy"] = _union_seconds(busy)                                    # wall time during which at least one lane had a copy or a kernel in flight
+    tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
 
 
 class ImprovedVideoCompressor:
@@ -210,6 +244,10 @@ class ImprovedVideoCompressor:
             self._lanes.append(_Lane(nat.Context(self._lanes[0].ctx.device), True))
         return self._lanes[:count]
 
+    def _on_lanes(self, jobs, fn):
+        """The results of fn(job, take) in job order, the jobs alternating over min(gpu_lanes, len(jobs)) lanes (_LanePool.map)."""
+        return _LanePool(self._get_lanes(min(self.gpu_lanes, len(jobs)))).map(jobs, fn)
+
     def _release_lanes(self):
         for lane in self._lanes:
             lane.release()
@@ -250,7 +288,7 @@ class ImprovedVideoCompressor:
         k, _l = self.inter.bloom_compressor._calculate_optimal_params(n, p)
         ones = int(np.count_nonzero(flat))
         stream = self._get_lanes(1)[0].sample_coder().encode_pair(a, b, np.packbits(flat.astype(np.uint8)), ones)
-        C = b.shape[2] if b.ndim == 3 else 1
+        _, _, C, _ = frame_geometry(b)
         return build_record(self.inter.wire_format, p, n, k, len(bitmap), np.packbits(bitmap).tobytes(), len(witness),
                             np.packbits(np.array(witness, dtype=np.uint8)).tobytes(), ones * C, stream)
 
@@ -270,15 +308,14 @@ class ImprovedVideoCompressor:
             return None
         if any(d.shape != a.shape or d.dtype != a.dtype for d in data[1:]):
             return None
-        H, W = a.shape[:2]
-        C = a.shape[2] if a.ndim == 3 else 1
+        H, W, C, sb = frame_geometry(a)
         if C > 4:                                # rbf_gather_values_batch carries at most 4 samples per pixel
             return [None] * (len(seg) - 1)
         if lane is None:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
         mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
-        coder = lane.coder(W, H, len(seg), C, a.dtype.itemsize, mc)
+        coder = lane.coder(W, H, len(seg), C, sb, mc)
         coder.set_run_starts(list(run_starts))
         block = _as_block(data)
         t1 = time.perf_counter()
@@ -331,16 +368,18 @@ class ImprovedVideoCompressor:
         """[(type, record)] for the frames with global indices [start, stop); frames[i] is global frame
         first_index + i (a shard passes its halo frame too, dist.halo_start).  Frame t is a keyframe iff
         t % keyframe_interval == 0; the inter-frames are coded in blocks of up to `block_frames` consecutive frames --
-        several GOPs per block, ONE launch sequence on the GPU per block, cut at the keyframes.  The blocks alternate over
+        several GOPs per block, ONE launch sequence on the GPU per block, cut at the keyframes (plan_range).  The blocks alternate over
         `gpu_lanes` contexts, each block on its own host thread; the host's zlib-9 (keyframes: four jobs each; changed values:
         one job per frame) runs on `num_threads` threads under all of it.  release: return the lanes' device memory as soon as the last
         block has left the GPU (False: keep the coders for the next call of the same geometry)."""
         records = {}
         I = self.keyframe_interval
+        inter_type = INTER_RICE if self.sample_codec == "rice" else INTER
         self.last_timing = tm = {}
         t_all = time.perf_counter()
         busy = []
         gpu_keys = set()                         # sample_codec="rice": keyframes coded as type-3 records on the lanes
+        fixed_keys, blocks = plan_range(first_index, start, stop, I, self.block_frames, inter_frames)
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
 
@@ -351,40 +390,16 @@ class ImprovedVideoCompressor:
                     gpu_keys.add(t)
                 else:
                     pending[t] = (KEY, self.compressor.compress_frame_jobs(frames[t - first_index], pool.submit))
+
+            def run_block(block, take):
+                lo, end, starts = block
+                with take() as lane:
+                    return self._encode_block(frames[lo - first_index:end - first_index], pool, starts, lane, busy)
             # the keyframes the rule fixes in advance go to the host threads FIRST: their zlib-9 (the longest single jobs, ~0.2 s for a 1080p
             # frame, plus its three planes) then runs under the GPU's blocks instead of behind the last one
-            for t in range(start, stop):
-                if not inter_frames or t % I == 0 or t - 1 < first_index:
-                    key(t)
-            blocks = []                                                      # (first frame read, end, run starts)
-            t = start
-            while t < stop:
-                if not inter_frames or t % I == 0 or t - 1 < first_index:
-                    t += 1
-                    continue
-                end = min(stop, t - 1 + self.block_frames)                   # the block reads frames t-1 .. end-1
-                blocks.append((t - 1, end, [u - (t - 1) for u in range(t, end) if u % I == 0]))      # keyframes inside the block: new runs
-                t = end
-            results = [None] * len(blocks)
-            if self.gop_batching and blocks:
-                import queue
-                lanes = self._get_lanes(min(self.gpu_lanes, len(blocks)))
-                free = queue.Queue()
-                for lane in lanes:
-                    free.put(lane)
-
-                def run_block(b):
-                    lo, end, starts = blocks[b]
-                    lane = free.get()
-                    try:
-                        return self._encode_block(frames[lo - first_index:end - first_index], pool, starts, lane, busy)
-                    finally:
-                        free.put(lane)
-                if len(lanes) == 1:
-                    results = [run_block(b) for b in range(len(blocks))]
-                else:
-                    with ThreadPoolExecutor(len(lanes)) as gpu_pool:
-                        results = list(gpu_pool.map(run_block, range(len(blocks))))
+            for t in fixed_keys:
+                key(t)
+            results = self._on_lanes(blocks, run_block) if self.gop_batching and blocks else [None] * len(blocks)
             tm["gpu_phase"] = time.perf_counter() - t_all                    # until the last block's values were on the host
             if release:                                                      # the lanes' blocks of frames, masks, filters and witnesses go back while the
                 t_rel = time.perf_counter()                                  # host threads still owe their zlib: not kept between videos
@@ -394,19 +409,18 @@ class ImprovedVideoCompressor:
                 seg = frames[lo - first_index:end - first_index]             # predecessor + the frames lo+1..end-1
                 for j in range(1, len(seg)):
                     u = lo + j
-                    if u % I == 0:
+                    if is_keyframe(u, first_index, I):
                         key(u)
                         continue
-                    fut = inter[j - 1] if inter is not None else None
                     if inter is None:                                        # not batchable (or gop_batching=False): frame by frame
                         rec = self._encode_inter(seg[j - 1], seg[j])
                         if rec is not None:
-                            records[u] = (INTER_RICE if self.sample_codec == "rice" else INTER, rec)
+                            records[u] = (inter_type, rec)
                             continue
-                    if fut is not None:
-                        pending[u] = (INTER, fut)
-                    else:
-                        key(u)
+                    elif inter[j - 1] is not None:
+                        pending[u] = (inter_type, inter[j - 1])
+                        continue
+                    key(u)
             if gpu_keys:
                 t_key = time.perf_counter()
                 for u, rec in self._encode_keys_rice(frames, first_index, sorted(gpu_keys), busy).items():
@@ -416,19 +430,15 @@ class ImprovedVideoCompressor:
                 tm["gpu_phase"] += time.perf_counter() - t_key
             t_wait = time.perf_counter()
             for u, (ty, fut) in pending.items():
-                rec = fut() if ty == KEY else fut.result()
-                records[u] = (INTER_RICE if ty == INTER and self.sample_codec == "rice" else ty, rec)
+                records[u] = (ty, fut() if ty == KEY else fut.result())
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
-        tm["total"] = time.perf_counter() - t_all
-        tm["gpu_busy"] = _union_seconds(busy)                                # wall time during which at least one lane had a copy or a kernel in flight
-        tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
+        _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
         return [records[u] for u in range(start, stop)]
 
     def _encode_keys_rice(self, frames, first_index, ts, busy):
         """Type-3 records of the keyframes with global indices `ts`: batches of up to four frames of one shape, ONE rbf_rice_encode_intra
         each, alternating over the GPU lanes like the blocks.  Returns {t: record}."""
-        import queue
         batches = []
         for t in ts:
             a = frame_data(frames[t - first_index])
@@ -436,26 +446,15 @@ class ImprovedVideoCompressor:
                 batches[-1][1].append(t)
             else:
                 batches.append(((a.shape, a.dtype), [t]))
-        lanes = self._get_lanes(min(self.gpu_lanes, len(batches)))
-        free = queue.Queue()
-        for lane in lanes:
-            free.put(lane)
 
-        def run(b):
-            fs = [frames[t - first_index] for t in batches[b][1]]
-            lane = free.get()
-            try:
+        def run(batch, take):
+            fs = [frames[t - first_index] for t in batch[1]]
+            with take() as lane:
                 t0 = time.perf_counter()
                 streams = lane.sample_coder().encode_frames(fs)
                 busy.append((t0, time.perf_counter()))
-            finally:
-                free.put(lane)
             return [key_record(f, s) for f, s in zip(fs, streams)]
-        if len(lanes) == 1:
-            outs = [run(b) for b in range(len(batches))]
-        else:
-            with ThreadPoolExecutor(len(lanes)) as gpu_pool:
-                outs = list(gpu_pool.map(run, range(len(batches))))
+        outs = self._on_lanes(batches, run)
         return {t: rec for (_, ts_b), recs in zip(batches, outs) for t, rec in zip(ts_b, recs)}
 
     def _decode_key_rice(self, rec, lane=None, busy=None):
@@ -491,13 +490,13 @@ class ImprovedVideoCompressor:
         self.last_compressed_frames = records
         keyframes = sum(1 for ty, _ in records if ty in KEYS)
         if output_path:
-            blob = self._container(records)
+            blob = container.write(records)
             os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
             with open(output_path, "wb") as f:
                 f.write(blob)
             compressed_size = len(blob)
         else:                                    # the container's size without joining ~1 MB per frame into one bytes object nobody asked for
-            compressed_size = self._container_size(records)
+            compressed_size = container.size(records)
         ratio = compressed_size / original_size
         elapsed = time.time() - start
         results = {"frame_count": len(frames), "original_size": original_size, "compressed_size": compressed_size,
@@ -513,52 +512,24 @@ class ImprovedVideoCompressor:
             print(f"Keyframes: {keyframes} ({results['keyframe_ratio'] * 100:.1f}%)")
         return results
 
-    @staticmethod
-    def _container(records):
-        all_key = all(ty == KEY for ty, _ in records)
-        out = [b"BFVC" if all_key else b"BFV2", struct.pack("<I", len(records))]
-        for ty, rec in records:
-            body = rec if all_key else struct.pack("<B", ty) + rec
-            out += [struct.pack("<I", len(body)), body]
-        return b"".join(out)
-
-    @staticmethod
-    def _container_size(records):
-        """len(_container(records)) without building it."""
-        extra = 0 if all(ty == KEY for ty, _ in records) else 1
-        return 8 + sum(4 + extra + len(rec) for _, rec in records)
+    _container = staticmethod(container.write)
+    _container_size = staticmethod(container.size)
+    _parse_container = staticmethod(container.parse)
 
     # ------------------------------------------------------------------ decode
-    @staticmethod
-    def _parse_container(blob):
-        magic = blob[:4]
-        if magic not in (b"BFVC", b"BFV2"):
-            raise ValueError(f"Invalid file format: {magic}")
-        (count,) = struct.unpack_from("<I", blob, 4)
-        off, records = 8, []
-        for _ in range(count):
-            (size,) = struct.unpack_from("<I", blob, off)
-            body = blob[off + 4: off + 4 + size]
-            off += 4 + size
-            records.append((KEY, body) if magic == b"BFVC" else (body[0], body[1:]))
-        return records
-
     def decompress_video(self, input_path=None, output_path=None, compressed_frames=None, metadata=None):
         start = time.time()
         t_all = time.perf_counter()
         records = None
         if input_path and os.path.exists(input_path):
             with open(input_path, "rb") as f:
-                records = self._parse_container(f.read())
+                records = container.parse(f.read())
         elif compressed_frames:
             records = [r if isinstance(r, tuple) else (KEY, r) for r in compressed_frames]
         if not records:
             raise ValueError("No compressed frames provided")
-        for ty, _ in records:
-            if ty not in KEYS + INTERS:
-                raise ValueError(f"unknown record type {ty}")
-        if records[0][0] in INTERS:
-            raise ValueError("inter-frame without a preceding keyframe")
+        types = [ty for ty, _ in records]
+        container.check_types(types)
         self.last_timing = tm = {}
         busy = []
         # the keyframes are independent of everything else: inflate them on the host threads while the inter-frame runs go through the GPU
@@ -566,84 +537,44 @@ class ImprovedVideoCompressor:
         key_pool = ThreadPoolExecutor(self.num_threads)
         keys = {j: key_pool.submit(self.compressor.decompress_frame, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
         gkeys = {}
-        runs = []                                                            # (index of the keyframe in front, first record, end)
-        i = 0
-        while i < len(records):
-            if records[i][0] in KEYS:
-                i += 1
-                continue
-            j = i
-            while j < len(records) and records[j][0] in INTERS:
-                j += 1
-            runs.append((i - 1, i, j))
-            i = j
+        runs = container.inter_runs(types)                                   # (index of the keyframe in front, first record, end)
         decoded = {}
+
+        def run_job(job, take):
+            k, lo, hi = job
+            base = keys[k].result() if types[k] == KEY else None             # (waits for the host's inflate without holding a lane)
+            with take() as lane:
+                if base is None:
+                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy)
+                if lo is None:
+                    return None
+                return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi])
         try:
             bases = {k for k, _, _ in runs}
-            lone = [j for j, (ty, _) in enumerate(records) if ty == KEY_RICE and j not in bases]
-            if self.gop_batching and (runs or lone):
+            jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty == KEY_RICE and j not in bases]     # lone type-3 keyframes: no run
+            if self.gop_batching and jobs:
                 # every run hangs off its own keyframe, so the runs are independent: they alternate over the lanes, each on its own host
                 # thread -- the inflate and upload of run r+1 under the device-side rebuild and the download of run r
-                import queue
-                jobs = [("run", r) for r in range(len(runs))] + [("key", j) for j in lone]
-                lanes = self._get_lanes(min(self.gpu_lanes, len(jobs)))
-                free = queue.Queue()
-                for lane in lanes:
-                    free.put(lane)
-
-                def run_job(job):
-                    kind, x = job
-                    k, lo, hi = runs[x] if kind == "run" else (x, None, None)
-                    base = keys[k].result() if records[k][0] == KEY else None
-                    lane = free.get()
-                    try:
-                        if base is None:
-                            base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy)
-                        if kind == "key":
-                            return None
-                        return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=[ty for ty, _ in records[lo:hi]])
-                    finally:
-                        free.put(lane)
-                if len(lanes) == 1:
-                    outs = [run_job(job) for job in jobs]
-                else:
-                    with ThreadPoolExecutor(len(lanes)) as gpu_pool:
-                        outs = list(gpu_pool.map(run_job, jobs))
-                for (kind, x), out in zip(jobs, outs):
-                    if kind == "run":
-                        decoded[runs[x][1]] = out
+                for (_, lo, _), out in zip(jobs, self._on_lanes(jobs, run_job)):
+                    if lo is not None:
+                        decoded[lo] = out
+            ends = {lo: hi for _, lo, hi in runs}
             frames = []
             i = 0
             while i < len(records):
-                ty, rec = records[i]
-                if ty in KEYS:
-                    if ty == KEY:
+                if i not in ends:                                            # a keyframe
+                    if types[i] == KEY:
                         frames.append(keys[i].result())
                     else:
-                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(rec))
+                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1]))
                     i += 1
                     continue
-                j = i
-                while j < len(records) and records[j][0] in INTERS:
-                    j += 1
-                if i in decoded:
-                    frames += decoded[i]
-                else:
-                    for ty2, r in records[i:j]:
-                        base = frames[-1]
-                        if ty2 == INTER_RICE:
-                            frames += self._decode_run(base, [r], types=[INTER_RICE])
-                            continue
-                        dtype = np.uint8 if r[0] == 1 else np.uint16
-                        mask, values = self.inter._decompress_frame_differences(r[1:], base.shape, dtype=dtype)
-                        frames.append(self.inter._apply_frame_diff(base, mask, values))
-                i = j
+                frames += decoded[i] if i in decoded else self._decode_frame_by_frame(frames[-1], records[i:ends[i]])
+                i = ends[i]
         finally:
             key_pool.shutdown(wait=True)
             self._release_lanes()
-        tm["total"] = time.perf_counter() - t_all
-        tm["gpu_busy"] = _union_seconds(busy)
-        tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
+        _close_timing(tm, t_all, busy)
         tm["runs"], tm["lanes"] = len(runs), min(self.gpu_lanes, max(1, len(runs)))
         if output_path:
             self.save_frames_as_video(frames, output_path)
@@ -651,17 +582,23 @@ class ImprovedVideoCompressor:
             print(f"Decompressed {len(frames)} frames in {time.time() - start:.2f} seconds")
         return frames
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None):
-        """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
-        ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
-        rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
-        (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2)."""
-        from .engine import apply_chain
-        if lane is None:
-            lane = self._get_lanes(1)[0]
-        types = [INTER] * len(recs) if types is None else list(types)
-        t0 = time.perf_counter()
-        base_arr = frame_data(base)
+    def _decode_frame_by_frame(self, base, records):
+        """The frames of a run of inter-frame records after `base`, one record at a time (gop_batching=False)."""
+        frames = []
+        for ty, r in records:
+            if ty == INTER_RICE:
+                frames += self._decode_run(base, [r], types=[INTER_RICE])
+            else:
+                dtype = np.uint8 if r[0] == 1 else np.uint16
+                mask, values = self.inter._decompress_frame_differences(r[1:], base.shape, dtype=dtype)
+                frames.append(self.inter._apply_frame_diff(base, mask, values))
+            base = frames[-1]
+        return frames
+
+    @staticmethod
+    def _parse_run(base_arr, recs, types):
+        """The records of a run after the frame `base_arr`, parsed ("f64" wire format) and checked against it; each dict also carries
+        `dtype` (of its values) and `rice` (a type-4 record: its value field is a sample stream)."""
         n = base_arr.shape[0] * base_arr.shape[1]
         parsed = []
         for ty, r in zip(types, recs):
@@ -675,6 +612,37 @@ class ImprovedVideoCompressor:
                 if (cnt, bits, size) != (d["value_count"], 8 * base_arr.dtype.itemsize, len(d["values_z"])) or d["dtype"] != base_arr.dtype:
                     raise ValueError("type-4 record: its sample stream (%d %d-bit samples, %d bytes) does not match the record" % (cnt, bits, size))
             parsed.append(d)
+        return parsed
+
+    @staticmethod
+    def _fit_values(parsed, masks, vals, n, ch):
+        """Every record's value count against its decoded mask (in place): a type-4 stream that does not fit its mask is an error, so is a
+        single-channel type-2 record; a colour frame with a mismatching value count is left untouched."""
+        for i, (m, v) in enumerate(zip(masks, vals)):
+            ones = _popcount(np.asarray(m, dtype=np.uint8)[:(n + 7) // 8])
+            if parsed[i]["rice"]:                # no reference behaviour to keep: a stream that does not fit its mask is an error
+                if parsed[i]["value_count"] != ones * ch:
+                    raise ValueError("type-4 record: %d residuals for a mask of %d pixels" % (parsed[i]["value_count"], ones))
+                continue
+            if len(v) != ones * ch:              # same rule as _apply_frame_diff (:886-903)
+                if ch == 1:
+                    raise ValueError("changed_values does not match the mask")
+                masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
+
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None):
+        """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
+        ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
+        rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
+        (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2)."""
+        from .engine import apply_chain
+        if lane is None:
+            lane = self._get_lanes(1)[0]
+        types = [INTER] * len(recs) if types is None else list(types)
+        t0 = time.perf_counter()
+        base_arr = frame_data(base)
+        H, W, ch, _ = frame_geometry(base_arr)
+        n = H * W
+        parsed = self._parse_run(base_arr, recs, types)
         inflate = lambda d: np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])[:d["value_count"]]
         own_pool = None
         if pool is None:
@@ -693,17 +661,7 @@ class ImprovedVideoCompressor:
             own_pool.shutdown()
         t3 = time.perf_counter()
         masks = [d["mask"] if "mask" in d else d["bitmap"][:(n + 7) // 8] for d in parsed]
-        ch = base_arr.shape[2] if base_arr.ndim == 3 else 1
-        for i, (m, v) in enumerate(zip(masks, vals)):
-            ones = _popcount(np.asarray(m, dtype=np.uint8)[:(n + 7) // 8])
-            if parsed[i]["rice"]:                # no reference behaviour to keep: a stream that does not fit its mask is an error
-                if parsed[i]["value_count"] != ones * ch:
-                    raise ValueError("type-4 record: %d residuals for a mask of %d pixels" % (parsed[i]["value_count"], ones))
-                continue
-            if len(v) != ones * ch:              # same rule as _apply_frame_diff (:886-903)
-                if ch == 1:
-                    raise ValueError("changed_values does not match the mask")
-                masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
+        self._fit_values(parsed, masks, vals, n, ch)
         t4 = time.perf_counter()
         out, prev, i = [], base_arr, 0
         while i < len(parsed):                   # stretches of one record type: values written (type 2) or residuals added (type 4)
