@@ -1,0 +1,348 @@
+// rbf_host.h -- what every entry point of rbf_api.hip stands on: the last-error text, the context and its scratch memory, per-kernel
+// timing, the process-wide pixel-index hash table, and the argument checks and launch helpers that several entry points share.
+#pragma once
+#include "rbf_plan.h"
+
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <new>
+#include <vector>
+
+// ------------------------------------------------------------------------------------------
+// errors
+// ------------------------------------------------------------------------------------------
+static thread_local char g_err[512] = "";
+
+static int fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                                    \
+    do {                                                                                                                 \
+        hipError_t e_ = (expr);                                                                                          \
+        if (e_ != hipSuccess)                                                                                            \
+            return fail(RBF_EIO, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);             \
+    } while (0)
+
+// ------------------------------------------------------------------------------------------
+// context
+// ------------------------------------------------------------------------------------------
+// Device scratch memory with one owner: grown on demand, never shrunk, freed with the context.  No pool and no cache: a buffer that
+// is too small is freed and allocated anew, and its contents are not kept.
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;                  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    int alloc(size_t bytes)          // exactly `bytes`
+    {
+        release();
+        HIP_TRY(hipMalloc((void **)&p, bytes));
+        cap = bytes;
+        return RBF_OK;
+    }
+    int reserve(size_t bytes) { return bytes <= cap ? RBF_OK : alloc(bytes + bytes / 4 + 256); }
+};
+
+struct Timed { int id; hipEvent_t a, b; };
+
+// The rows of a batch: masks, filters, witnesses (and, on the encode side, stats).  Encode reads the masks and writes the rest; decode
+// reads filters and witnesses and writes the masks.
+struct BloomBatch {
+    void *masks; uint64_t mask_stride;
+    uint64_t n; uint32_t nframes; const rbf_filter_params *params; const rbf_seeds *seeds;
+    void *filters; uint64_t filter_stride;
+    void *witnesses; uint64_t witness_stride;
+    uint64_t *stats;
+    // frames first .. first + count - 1
+    BloomBatch rows(uint32_t first, uint32_t count) const
+    {
+        BloomBatch b = *this;
+        b.nframes = count; b.params = params + first;
+        b.masks = (uint8_t *)masks + (uint64_t)first * mask_stride;
+        b.filters = (uint8_t *)filters + (uint64_t)first * filter_stride;
+        b.witnesses = (uint8_t *)witnesses + (uint64_t)first * witness_stride;
+        if (stats) b.stats = stats + (uint64_t)first * RBF_STATS_PER_FRAME;
+        return b;
+    }
+    BloomBatch with(const rbf_filter_params *other) const { BloomBatch b = *this; b.params = other; return b; }
+};
+
+struct rbf_ctx {
+    int device = 0;
+    uint32_t cus = 256;              // compute units of the device (hipDeviceAttributeMultiprocessorCount; MI355X: 256)
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    Knobs knobs;                     // rbf_ctx_force_generic / rbf_ctx_option
+    // scratch
+    DevBuf<uint32_t> seg_cnt;
+    DevBuf<uint64_t> seg_off;
+    DevBuf<uint32_t> chunk_off;      // k_chunk_offsets: where every compaction / expansion workgroup's witness bits start
+    DevBuf<uint64_t> pass_words;
+    DevBuf<uint32_t> partials;
+    DevBuf<uint2> ins_records;       // two-kernel insert: 8 bytes per set mask bit of the batch
+    DevBuf<uint32_t> ins_counters;   // ... and the records appended so far, per frame
+    DevBuf<uint64_t> ones_acc;       // where the mask kernels count; k_finish_ones hands the counts out and re-zeroes it
+    bool ones_acc_dirty = false;     // a call failed between the mask kernels and k_finish_ones
+    DevBuf<uint32_t> mask_ticket;    // the fused tail of the GOP mask kernel: workgroups done so far (zero between launches)
+    DevBuf<uint32_t> qimage;         // probe image of the batch's filters (FP64 query kernel)
+    DevBuf<int32_t> thr_tab;         // per-pair thresholds of the mask kernels
+    DevBuf<uint64_t> pack_base;      // running record size between pack chunks; per-row totals of count_and_scan_masks
+    // sample codec (rbf_kernels_rice.h)
+    DevBuf<uint16_t> rice_u;         // u values (encode) / s values (decode) of the call's streams
+    DevBuf<uint32_t> rice_kw;        // per chunk: k | words << 8
+    DevBuf<uint64_t> rice_off;       // per chunk: payload word offset (+ the total), then per stream
+    DevBuf<void> rice_tab;           // the call's stream / chunk table
+    DevBuf<void> rice_blob;          // uploaded streams (decode)
+    DevBuf<uint32_t> rice_err;       // decode / apply error flag
+    struct SharedHashTable *hash_shared = nullptr;                // the pixel-index hash table this context holds a reference to
+    uint4 *hash_tab = nullptr;                                    // = hash_shared->table
+    // host staging of encode_gop: device-visible pinned block [flag | ones...] the GPU publishes into
+    uint64_t *ones_pinned = nullptr; size_t host_cap = 0;
+    uint64_t *ones_mapped_dev = nullptr;     // device address of the same block
+    uint64_t publish_token = 0;
+    struct PendingGop {                      // between rbf_encode_gop_begin and rbf_encode_gop_finish
+        bool active = false;
+        uint64_t token = 0; rbf_seeds seeds{};
+        BloomBatch batch{};                      // the caller's buffers; params and seeds are set by the second half
+        bool has_skip = false;                   // ctx->run_skip[p] != 0: pair p crosses a keyframe and is not coded
+    } gop;
+    std::vector<uint8_t> run_skip;
+    std::vector<rbf_filter_params> plan;
+    std::vector<double> plan_k;
+    // timing
+    uint32_t timing = 0;             // bit k: bracket launches of kernel id k with HIP events
+    std::vector<Timed> pending;
+    std::vector<hipEvent_t> pool;
+    double total_ms[RBF_K_COUNT] = {0};
+    uint64_t launches[RBF_K_COUNT] = {0};
+
+    ~rbf_ctx() { if (ones_pinned) (void)hipHostFree(ones_pinned); }     // (the DevBuf members free themselves)
+};
+
+// Every entry point starts here.
+static int set_device(rbf_ctx *ctx)
+{
+    if (!ctx) return fail(RBF_EINVAL, "null context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return RBF_OK;
+}
+
+struct LaunchTimer {
+    rbf_ctx *c; int id; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
+    LaunchTimer(rbf_ctx *ctx, int kid /* < 0: never timed */) : c(ctx), id(kid), on(kid >= 0 && ((ctx->timing >> kid) & 1u)), st(ctx->stream)
+    {
+        if (!on) return;
+        auto get = [&]() {
+            hipEvent_t e = nullptr;
+            if (!c->pool.empty()) { e = c->pool.back(); c->pool.pop_back(); }
+            else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+            return e;
+        };
+        a = get(); b = get();
+        if (!a || !b) { on = false; return; }
+        (void)hipEventRecord(a, st);
+    }
+    ~LaunchTimer()
+    {
+        if (!on) return;
+        (void)hipEventRecord(b, st);
+        try { c->pending.push_back({id, a, b}); }                 // timing is best effort; nothing may throw across the C ABI
+        catch (...) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    }
+};
+
+static int drain_timing(rbf_ctx *ctx)
+{
+    if (ctx->pending.empty()) return RBF_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (auto &t : ctx->pending) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
+            ctx->total_ms[t.id] += ms;
+            ctx->launches[t.id] += 1;
+        }
+        try { ctx->pool.push_back(t.a); } catch (...) { (void)hipEventDestroy(t.a); }
+        try { ctx->pool.push_back(t.b); } catch (...) { (void)hipEventDestroy(t.b); }
+    }
+    ctx->pending.clear();
+    return RBF_OK;
+}
+
+static int allow_big_lds(const void *fn)
+{
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+    return RBF_OK;
+}
+
+static inline Seeds to_dev(const rbf_seeds &s) { return Seeds{s.h1, s.h2, s.act}; }
+template <class A, class B> static inline bool same_seeds(const A &a, const B &b) { return a.h1 == b.h1 && a.h2 == b.h2 && a.act == b.act; }
+
+// ------------------------------------------------------------------------------------------
+// The pixel-index hash table (k_hash_table, 26 bytes per pixel inside an allocation of 32: rbf_kernels_q64.h) depends on the
+// device, the frame size and the seeds only, so the contexts of one process SHARE it: four pipelines coding 1080p GOPs gather from
+// one 54 MB table that the 256 MB Infinity Cache can keep, instead of four private ones that it cannot (measured: 0.197 -> 0.18x ms
+// per step).  Built once by the first context that needs it (on its stream; the others make their streams wait for the `ready`
+// event), freed when the last reference goes.
+// ------------------------------------------------------------------------------------------
+struct SharedHashTable {
+    int device; uint64_t n; rbf_seeds seeds;
+    uint4 *table; size_t bytes;
+    hipEvent_t ready;
+    int refs;
+    bool is_for(int dev, uint64_t pixels, const rbf_seeds &s) const { return device == dev && n == pixels && same_seeds(seeds, s); }
+};
+static std::mutex g_hash_mu;
+static std::vector<SharedHashTable *> g_hash_tables;
+
+static void hash_table_free(SharedHashTable *t)
+{
+    if (t->ready) (void)hipEventDestroy(t->ready);
+    (void)hipFree(t->table);
+    delete t;
+}
+
+static void hash_table_release(rbf_ctx *ctx)
+{
+    SharedHashTable *t = ctx->hash_shared;
+    if (!t) return;
+    (void)hipStreamSynchronize(ctx->stream);                      // my kernels no longer read it
+    ctx->hash_shared = nullptr; ctx->hash_tab = nullptr;
+    std::lock_guard<std::mutex> lk(g_hash_mu);
+    if (--t->refs > 0) return;
+    for (size_t i = 0; i < g_hash_tables.size(); ++i)
+        if (g_hash_tables[i] == t) { g_hash_tables[i] = g_hash_tables.back(); g_hash_tables.pop_back(); break; }
+    hash_table_free(t);
+}
+
+static void launch_hash_table(rbf_ctx *ctx, uint64_t n, const Seeds &sd, uint4 *table)
+{
+    const uint64_t segs = (n + QL_SEG_PIXELS - 1) / QL_SEG_PIXELS;
+    LaunchTimer timer(ctx, RBF_K_HASHTAB);
+    hipLaunchKernelGGL(k_hash_table, dim3((uint32_t)((segs + HT_THREADS / WAVE - 1) / (HT_THREADS / WAVE))), dim3(HT_THREADS), 0,
+                       ctx->stream, n, sd, table);
+}
+
+// The table of (ctx->device, n, seeds) in ctx->hash_tab, built if nobody has it yet (*built).  false: no device memory (the caller
+// hashes in the insert kernel instead).
+static bool hash_table_acquire(rbf_ctx *ctx, uint64_t n, const rbf_seeds &seeds, bool *built)
+{
+    *built = false;
+    if (ctx->hash_shared && ctx->hash_shared->is_for(ctx->device, n, seeds)) return true;
+    hash_table_release(ctx);
+    std::lock_guard<std::mutex> lk(g_hash_mu);
+    for (SharedHashTable *t : g_hash_tables)
+        if (t->is_for(ctx->device, n, seeds)) {
+            if (hipStreamWaitEvent(ctx->stream, t->ready, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+            ++t->refs;
+            ctx->hash_shared = t; ctx->hash_tab = t->table;
+            return true;
+        }
+    SharedHashTable *t = new (std::nothrow) SharedHashTable{ctx->device, n, seeds, nullptr, hash_table_bytes(n), nullptr, 1};
+    if (!t) return false;
+    if (hipMalloc((void **)&t->table, t->bytes) != hipSuccess || hipEventCreateWithFlags(&t->ready, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        hash_table_free(t);
+        return false;
+    }
+    launch_hash_table(ctx, n, to_dev(seeds), t->table);
+    // a table whose kernel never ran must not be published to the other contexts of the process
+    bool ok = hipGetLastError() == hipSuccess && hipEventRecord(t->ready, ctx->stream) == hipSuccess;
+    if (ok) try { g_hash_tables.push_back(t); } catch (...) { ok = false; }
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(ctx->stream);
+        hash_table_free(t);
+        return false;
+    }
+    ctx->hash_shared = t; ctx->hash_tab = t->table;
+    *built = true;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------
+// shared argument checks
+// ------------------------------------------------------------------------------------------
+static int check_frame_geometry(uint64_t n, uint32_t nframes, uint64_t mask_stride_bytes)
+{
+    if (n == 0 || n > 0xFFFFFFFFull) return fail(RBF_ERANGE, "n = %llu outside [1, 2^32-1]", (unsigned long long)n);
+    if (nframes == 0) return fail(RBF_EINVAL, "nframes must be >= 1");
+    if (mask_stride_bytes % 8 || mask_stride_bytes < ((n + 63) / 64) * 8)
+        return fail(RBF_EINVAL, "mask stride %llu must be a multiple of 8 and >= %llu", (unsigned long long)mask_stride_bytes,
+                    (unsigned long long)(((n + 63) / 64) * 8));
+    return RBF_OK;
+}
+
+static int check_witness_stride(uint64_t n, uint64_t witness_stride_bytes)
+{
+    if (witness_stride_bytes % 8 || witness_stride_bytes < ((n + 63) / 64) * 8) return fail(RBF_EINVAL, "witness stride too small or misaligned");
+    return RBF_OK;
+}
+
+// How an entry point's frames lie in memory (bytes), and what the entry point asks of that layout.
+struct FrameLayout {
+    uint32_t width, height;
+    uint64_t row_pitch;
+    uint32_t pixel_stride, sample_bytes;
+    uint64_t frame_stride;           // 0: a single frame
+};
+struct LayoutRules {
+    uint32_t samples = 1;            // samples of a pixel the entry point touches: the pixel stride has to hold them
+    bool channels = false;           // `samples` is the caller's channel count: 1..4
+    bool aligned = true;             // pixel stride, row pitch and frame stride are multiples of the sample size
+    uint32_t min_frames = 0, max_frames = 0xFFFFFFFFu;
+    uint32_t max_height = 0;         // 0: any
+};
+
+static int check_layout(const FrameLayout &l, uint32_t nframes, const LayoutRules &r)
+{
+    if (nframes < r.min_frames || nframes > r.max_frames)
+        return fail(RBF_EINVAL, "frame count %u out of range %u..%u", nframes, r.min_frames, r.max_frames);
+    if (l.width == 0 || l.height == 0) return fail(RBF_EINVAL, "empty frame %ux%u", l.width, l.height);
+    if (r.max_height && l.height > r.max_height) return fail(RBF_ERANGE, "at most %u rows, got %u", r.max_height, l.height);
+    if (l.sample_bytes != 1 && l.sample_bytes != 2) return fail(RBF_EINVAL, "sample_bytes must be 1 or 2, got %u", l.sample_bytes);
+    if (r.channels && (r.samples == 0 || r.samples > 4)) return fail(RBF_EINVAL, "channels must be 1..4, got %u", r.samples);
+    if (l.pixel_stride < r.samples * l.sample_bytes || (r.aligned && l.pixel_stride % l.sample_bytes))
+        return fail(RBF_EINVAL, "pixel stride %u incompatible with %u sample(s) of %u bytes", l.pixel_stride, r.samples, l.sample_bytes);
+    if (l.row_pitch < (uint64_t)l.width * l.pixel_stride || (r.aligned && l.row_pitch % l.sample_bytes))
+        return fail(RBF_EINVAL, "row pitch %llu too small or misaligned", (unsigned long long)l.row_pitch);
+    if (r.aligned && l.frame_stride % l.sample_bytes) return fail(RBF_EINVAL, "frame stride misaligned");
+    return RBF_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// shared launches
+// ------------------------------------------------------------------------------------------
+// Calls f with a zero of the sample type, so that a launch templated on it names its argument list once:
+//   by_sample_width(sample_bytes, [&](auto s) { hipLaunchKernelGGL(k_x<decltype(s)>, ...); });
+template <class F> static void by_sample_width(uint32_t sample_bytes, F &&f)
+{
+    if (sample_bytes == 1) f(uint8_t{});
+    else f(uint16_t{});
+}
+
+// The set bits of `rows` mask rows of n pixels per 1024-pixel segment (ctx->seg_cnt), their exclusive scan per row (ctx->seg_off)
+// and every row's total (totals_out, nullable).
+static int count_and_scan_masks(rbf_ctx *ctx, const void *masks_dev, uint64_t mask_stride_bytes, uint64_t n, uint32_t rows, uint64_t *totals_out)
+{
+    const uint64_t nseg = (n + SEG_PIXELS - 1) / SEG_PIXELS;
+    if (int r = ctx->seg_cnt.reserve((size_t)rows * nseg * 4)) return r;
+    if (int r = ctx->seg_off.reserve((size_t)rows * nseg * 8)) return r;
+    hipLaunchKernelGGL(k_mask_segment_counts, dim3((uint32_t)((nseg + WG_WAVES - 1) / WG_WAVES), rows), dim3(WG_THREADS), 0, ctx->stream,
+                       (const uint64_t *)masks_dev, mask_stride_bytes / 8, n, ctx->seg_cnt.p, nseg);
+    hipLaunchKernelGGL(k_scan_segments, dim3(rows), dim3(1024), 0, ctx->stream, ctx->seg_cnt.p, ctx->seg_off.p, nseg, totals_out, 1u);
+    return RBF_OK;
+}

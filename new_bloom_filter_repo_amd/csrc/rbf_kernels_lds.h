@@ -1008,4 +1008,41 @@ __global__ __launch_bounds__(WG_THREADS) void k_residual_mask_any_gop(
 #include "rbf_kernels_mask_body.h"
 }
 
+// per-pair thresholds travel as kernel arguments (captured at launch) into a device table
+struct ThrChunk {
+    static constexpr uint32_t N = 256;
+    int32_t v[N];
+};
+__global__ void k_store_thresholds(const ThrChunk c, int32_t *__restrict__ dst, uint32_t count)
+{
+    if (threadIdx.x < count) dst[threadIdx.x] = c.v[threadIdx.x];
+}
+
+// The tail of a residual-mask pass, ONE launch instead of a memset in front of the mask kernels, a copy kernel behind
+// them and two more memsets (rocprofv3: the four small launches were ~25 us of a ~215 us step).  The mask kernels count
+// into a context-owned accumulator that is zero whenever they start; block 0 hands the counts to the caller's array (and,
+// for rbf_encode_gop, into the device-visible pinned block whose flag word the host spins on) and zeroes the accumulator
+// again; every block clears its share of up to two output regions (the witness rows and the stats of the batch).
+__global__ __launch_bounds__(256) void k_finish_ones(uint64_t *__restrict__ acc, uint64_t *__restrict__ ones, uint32_t count,
+                                                     uint64_t *host_block /* nullable */, uint64_t token,
+                                                     uint4 *__restrict__ clear_a, uint64_t quads_a, uint4 *__restrict__ clear_b, uint64_t quads_b)
+{
+    if (blockIdx.x == 0) {
+        for (uint32_t i = threadIdx.x; i < count; i += blockDim.x) {
+            const uint64_t v = acc[i];
+            ones[i] = v;
+            acc[i] = 0;
+            if (host_block) __hip_atomic_store(&host_block[1 + i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        if (host_block) {
+            __threadfence_system();
+            __syncthreads();
+            if (threadIdx.x == 0) __hip_atomic_store(&host_block[0], token, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < quads_a; i += (uint64_t)gridDim.x * blockDim.x) clear_a[i] = z;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < quads_b; i += (uint64_t)gridDim.x * blockDim.x) clear_b[i] = z;
+}
+
 }  // namespace rbf
