@@ -102,7 +102,7 @@ _lib = None
 
 
 def exported_symbols():
-    """Names include/rbf.h declares (kept in sync by tests/test_abi.py)."""
+    """Names include/rbf.h declares (kept in sync by tests/test_host_cpu.py::test_abi_header_matches_binding_and_library)."""
     return sorted(_PROTOS)
 
 

@@ -1,10 +1,19 @@
 // rbf_api.hip -- C ABI (include/rbf.h) over the gfx950 kernels: the mask stage, the encode / decode chunks and the entry points, in
-// the order of the header.  One translation unit, split by #include like the kernels:
-//   rbf_plan.h       which kernels serve a batch (pure host code)
+// the order of the header.  One translation unit, split by #include:
+//   rbf_plan.h       which kernels serve a batch, and the frame tables they read (pure host code over rbf_geometry.h)
 //   rbf_host.h       errors, context and scratch memory, timing, the shared hash table, shared argument checks and launches
 //   rbf_rice_host.h  host side of the sample codec
+// and the kernels it launches, one header per stage (rbf_kernels.h: the generic path):
 #include "rbf_host.h"
+#include "rbf_kernels.h"
 #include "rbf_kernels_noise.h"
+#include "rbf_kernels_mask.h"
+#include "rbf_kernels_barrett.h"
+#include "rbf_kernels_insert_f64.h"
+#include "rbf_kernels_reduce.h"
+#include "rbf_kernels_query_f64.h"
+#include "rbf_kernels_query_f64_tiled.h"
+#include "rbf_kernels_witness.h"
 #include "rbf_kernels_pack.h"
 #include "rbf_rice_host.h"
 
@@ -324,7 +333,7 @@ static int launch_query(rbf_ctx *ctx, const Plan &pl, const BloomBatch &b, const
     uint32_t nactive; uint64_t empty[2];
     LaunchTimer t(ctx, RBF_K_QUERY);
     if (pl.query == QueryKind::LdsTiledF64) {
-        const FrameTable stab = query_table_s64(tab, nframes, &nactive, empty);
+        const FrameTable stab = query_table(tab, nframes, nullptr, &nactive, empty);
         if (flags.quiet_passthrough) empty[0] = empty[1] = 0;
         // 0: every coded frame has floor(k*) 1 or 2; 1: 0, 1 or 2; 2: anything (all frames walk their probes per tile)
         int mode = 0;
@@ -341,7 +350,7 @@ static int launch_query(rbf_ctx *ctx, const Plan &pl, const BloomBatch &b, const
         uint4 *table_out = flags.table_for_next ? table_to_rewrite(ctx, b.n, sd) : nullptr;
         // k_query_u64: coded frames ordered by floor(k*), 32-byte frame records in LDS behind the two image buffers
         U64Classes cls;
-        const FrameTable utab = query_table_u64(tab, nframes, &nactive, &cls, empty);
+        const FrameTable utab = query_table(tab, nframes, &cls, &nactive, empty);
         if (flags.quiet_passthrough) empty[0] = empty[1] = 0;
         // the 111-register kernel (two waves of a neighbour pipeline's mask / compaction kernels fit next to it on every SIMD) unless the
         // batch has floor(k*) = 4 or 5, which only the 118-register one passes in rows

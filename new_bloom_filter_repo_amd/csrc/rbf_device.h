@@ -4,6 +4,8 @@
 // MSB-first bit addressing used by every packed bit vector at the ABI.
 // Reference semantics: improved_video_compressor.py:65-97 (see include/rbf.h).
 #pragma once
+#include "rbf_geometry.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -14,24 +16,6 @@ constexpr uint64_t P2 = 0xC2B2AE3D27D4EB4FULL;
 constexpr uint64_t P3 = 0x165667B19E3779F9ULL;
 constexpr uint64_t P4 = 0x85EBCA77C2B2AE63ULL;
 constexpr uint64_t P5 = 0x27D4EB2F165667C5ULL;
-
-constexpr int WAVE = 64;
-
-// Per-frame filter geometry as the kernels see it.
-struct FrameDev {
-    uint32_t m;        // filter bits
-    uint32_t floor_k;  // deterministic probes
-    uint64_t T;        // activation threshold: extra probe iff h_act < T
-    uint64_t M;        // floor(2^64 / m) for m >= 2 (Barrett reciprocal); unused when m == 1
-};
-
-struct Seeds { uint64_t h1, h2, act; };
-
-// A batch's geometry travels BY VALUE in the kernel-argument segment (3 KiB of the 4 KiB limit):
-// no upload, no device buffer, and the per-frame fields arrive through scalar loads.
-constexpr int MAX_BATCH = 128;
-struct FrameTable { FrameDev f[MAX_BATCH]; };
-struct SliceTable { uint8_t n[MAX_BATCH]; };     // insert: partial filters (mask slices) per frame, 0 = frame not coded
 
 // 32-bit words of an m-bit filter; m may be 2^32 - 1, so the rounding is done in 64 bits
 __device__ __forceinline__ uint32_t filter_words(uint32_t m) { return (uint32_t)(((uint64_t)m + 31u) >> 5); }
@@ -248,7 +232,7 @@ __device__ __forceinline__ bool hash3_run8(uint32_t v0, uint32_t valid, const Se
     return false;
 }
 
-// Hashes of v0 + j, j = 0..3 (a lane of k_query_p4 owns 4 consecutive indices): the same decade-prefix sharing as
+// Hashes of v0 + j, j = 0..3 (a lane of round 2's k_query_p4, git history, owned 4 consecutive indices): the same decade-prefix sharing as
 // hash3_run8 -- a run of 4 touches at most two decades.  Returns false (nothing written) when the wave cannot take the
 // shared-prefix path; the caller then hashes index by index.
 template <int LEN>

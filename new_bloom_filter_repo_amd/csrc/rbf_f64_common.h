@@ -1,9 +1,11 @@
-// rbf_kernels_q64.h -- what the FP64 kernels share (k_query_u64, k_query_s64t, k_insert_tab, k_insert_positions; filters of
-// 2^15 <= m < 2^23 bits): the exact h mod m through one v_fma_f64, the probe image, activation ranks, the pixel-index hash table's
-// layout and the LDS-DMA of an image row.  (Rounds 2 and 3 kept their query kernels k_query_f64 / f64t / p4 / r64 here and in
-// rbf_kernels_r64.h; they are history now: git keeps them, tools/legacy/ up to round 4.)
+// rbf_f64_common.h -- what the FP64 kernels share (k_query_u64, k_query_s64t, k_insert_tab, k_insert_positions; filters of
+// 2^15 <= m < 2^23 bits): the exact h mod m through one v_fma_f64, the probe image, activation ranks and the pixel-index hash table's
+// layout.  (The LDS-DMA of an image row is in rbf_lds_dma.h; the query kernels of rounds 2 and 3 that lived here are in the git history.)
 #pragma once
-#include "rbf_kernels_lds.h"
+#include "rbf_geometry.h"
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace rbf {
 
@@ -17,7 +19,7 @@ namespace rbf {
 // only r_est mod 2^24 is needed (|r_est| < 2^23 as m < 2^23), and that depends only on the low 24 bits of q_est, m
 // and h: ONE v_mad_u32_u24 computes (-q_est * m + h_lo) mod 2^24, v_bfe_i32 sign-extends it, and one add +
 // unsigned min folds a negative r_est back into [0, m).  Exactness is checked against integer arithmetic on the host
-// (tests/c/mod_f64_check.c restates these five steps in C) and by the GPU parity tests.  (rows_reduce4, rbf_kernels_s64.h,
+// (tests/c/mod_f64_check.c restates these five steps in C) and by the GPU parity tests.  (rows_reduce4, rbf_query_f64_pass.h,
 // takes the remainder as a full signed 32-bit number with one v_mad_u64_u32 instead: no sign extension.)
 __device__ __forceinline__ uint32_t mod_m_f64(double hd, uint32_t hl, double ninv, uint32_t m)
 {
@@ -28,7 +30,6 @@ __device__ __forceinline__ uint32_t mod_m_f64(double hd, uint32_t hl, double nin
     const uint32_t rs = (uint32_t)(((int32_t)(r << 8)) >> 8);                     // v_bfe_i32 r, 0, 24
     return min(rs, rs + m);
 }
-constexpr uint32_t F64MOD_M_MIN = 1u << 15, F64MOD_M_MAX = (1u << 23) - 1u;      // eligible filter sizes (host: make_plan)
 
 __device__ __forceinline__ uint32_t vgpr_copy(uint32_t uniform)
 {
@@ -84,7 +85,7 @@ __device__ __forceinline__ uint32_t select_or_ones(uint64_t mask, uint32_t if_se
 }
 
 // ---- the pixel-index hash table ----------------------------------------------------------------------------------
-// What k_insert_tab gathers instead of hashing (rbf_kernels_i64.h): three arrays over the frame's indices, padded to whole 512-index
+// What k_insert_tab gathers instead of hashing (rbf_kernels_insert_f64.h): three arrays over the frame's indices, padded to whole 512-index
 // segments (`hash_table_entries`), 26 bytes per index inside an allocation of 32:
 //     pos[slot]   16 bytes: h1, h2                 -- ONE 16-byte load per key.  Rounds 2 and 3 kept 32-byte entries (RN(h1), RN(h2) as
 //                                                    doubles | low dwords | h_act) and read them with two loads: the texture addresser
@@ -126,32 +127,5 @@ __device__ __forceinline__ void hash_table_store8(uint4 *__restrict__ table, uin
 }
 // RN(h) as a double from the two halves of h: both conversions and the product are exact, the sum is rounded once
 __device__ __forceinline__ double rn_double(uint32_t lo, uint32_t hi) { return __builtin_fma((double)hi, 0x1p32, (double)lo); }
-
-// ---- LDS-DMA of an image row -------------------------------------------------------------------------------------
-// `words` dwords of `row` -> LDS at lds_byte_addr, 1 KiB (one 16-byte piece per lane) per wave and step, the row pointer in an SGPR
-// pair (saddr addressing: the VGPR holds a 32-bit byte offset), bounds tested only on the row's last piece.  M0 is saved and
-// restored inside the asm block (a reserved register: the compiler rejects it as a clobber).  Completion: dma_wait_all().
-__device__ __forceinline__ void dma_row(uint32_t lds_byte_addr /* uniform */, const uint32_t *row /* uniform */, uint32_t words, uint32_t wave, uint32_t lane, uint32_t nwaves)
-{
-    const uint32_t npieces = words >> 2;                          // whole 16-byte pieces
-    const uint32_t lane_off = lane << 4;
-    for (uint32_t c = wave; (c << 6) < npieces; c += nwaves) {
-        const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr + (c << 10));
-        const uint32_t off = lane_off + (c << 10);
-        if ((c << 6) + 64u <= npieces || (c << 6) + lane < npieces) {
-            uint32_t keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "s"(dst), "v"(off), "s"(row) : "memory");
-        }
-    }
-    const uint32_t tail = words & 3u;                             // 0..3 dwords left: 4-byte DMA by wave 0
-    if (wave == 0 && lane < tail) {
-        const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr + (npieces << 4));
-        const uint32_t off = (npieces << 4) + (lane << 2);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "s"(dst), "v"(off), "s"(row) : "memory");
-    }
-}
 
 }  // namespace rbf

@@ -1,6 +1,8 @@
 // rbf_host.h -- what every entry point of rbf_api.hip stands on: the last-error text, the context and its scratch memory, per-kernel
 // timing, the process-wide pixel-index hash table, and the argument checks and launch helpers that several entry points share.
 #pragma once
+#include "rbf_kernels.h"
+#include "rbf_kernels_insert_f64.h"
 #include "rbf_plan.h"
 
 #include <cstdarg>
@@ -192,7 +194,7 @@ static inline Seeds to_dev(const rbf_seeds &s) { return Seeds{s.h1, s.h2, s.act}
 template <class A, class B> static inline bool same_seeds(const A &a, const B &b) { return a.h1 == b.h1 && a.h2 == b.h2 && a.act == b.act; }
 
 // ------------------------------------------------------------------------------------------
-// The pixel-index hash table (k_hash_table, 26 bytes per pixel inside an allocation of 32: rbf_kernels_q64.h) depends on the
+// The pixel-index hash table (k_hash_table, 26 bytes per pixel inside an allocation of 32: rbf_f64_common.h) depends on the
 // device, the frame size and the seeds only, so the contexts of one process SHARE it: four pipelines coding 1080p GOPs gather from
 // one 54 MB table that the 256 MB Infinity Cache can keep, instead of four private ones that it cannot (measured: 0.197 -> 0.18x ms
 // per step).  Built once by the first context that needs it (on its stream; the others make their streams wait for the `ready`

@@ -8,12 +8,11 @@
 // kernels see are natural order (bit l = lane l).
 #pragma once
 #include "rbf_device.h"
+#include "rbf_geometry.h"
 
 namespace rbf {
 
-constexpr int SEG_PIXELS = 1024;                 // pixels per segment (one wave)
 constexpr int SEG_ITERS = SEG_PIXELS / WAVE;     // 16
-constexpr int WG_THREADS = 256;
 constexpr int WG_WAVES = WG_THREADS / WAVE;      // 4
 
 // ---- wave-wide sums without LDS: DPP adds (a __shfl_* is a ds_bpermute round trip through LDS on gfx950) ------------------------

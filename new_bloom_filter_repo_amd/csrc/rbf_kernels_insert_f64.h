@@ -1,14 +1,14 @@
-// rbf_kernels_i64.h -- the insert path for filters of 2^15 <= m < 2^23 bits (1080p / 2160p frames):
+// rbf_kernels_insert_f64.h -- the insert path for filters of 2^15 <= m < 2^23 bits (1080p / 2160p frames):
 //
 //   k_hash_table   the three XXH64 of EVERY pixel index of the frame geometry (they depend on the index and the seeds
 //                  only, not on the frame: improved_video_compressor.py:77-78,94).  Runs for the FIRST batch of a
 //                  geometry; afterwards a context that holds the table alone has k_query_u64, which computes the same hashes for
 //                  its own probes in every batch, write it again for the following batch's insert (to keep it cached).  Layout:
-//                  rbf_kernels_q64.h (16-byte (h1, h2) entries, 16-bit activation tags, the full h_act for ties).  A lane
+//                  rbf_f64_common.h (16-byte (h1, h2) entries, 16-bit activation tags, the full h_act for ties).  A lane
 //                  owns 8 consecutive indices, so the decade-prefix sharing of hash3_run8 applies (~120 instead of ~600
 //                  instructions per index), and over a 29-frame batch 93 % of all indices are set in at least one frame, so
 //                  nothing is hashed in vain.
-//   k_insert_tab   k_insert_lds with the hashing replaced by ONE 16-byte gather (+ a 2-byte tag) from that table: workgroup
+//   k_insert_tab   k_insert_lds (rbf_kernels_barrett.h) with the hashing replaced by ONE 16-byte gather (+ a 2-byte tag) from that table: workgroup
 //                  (slice, frame[, tile]) builds a partial filter in LDS from its slice of the mask; set positions are compacted
 //                  through a per-wave LDS queue so that the gather, the two reductions (mod_m_f64) and the LDS atomics
 //                  always run on full waves; the gather of one batch of 64 keys flies while the next mask bytes are
@@ -17,9 +17,11 @@
 //                  other frames.
 //
 // In k_insert_lds the three hashes of the p*n set positions cost ~33 of its ~70 us per 1080p x 29 batch (64-bit
-// multiplies: tools/bench_insert.hip ablation); the table costs one ~54 MB write, once.
+// multiplies: round 2's insert ablation, git history); the table costs one ~54 MB write, once.
 #pragma once
-#include "rbf_kernels_q64.h"
+#include "rbf_f64_common.h"
+#include "rbf_kernels.h"
+#include "rbf_lds_dma.h"
 
 namespace rbf {
 
@@ -50,11 +52,6 @@ __global__ __launch_bounds__(HT_THREADS) void k_hash_table(uint64_t n, Seeds see
     hash_table_store8(table, n, seg, lane, h1, h2, ha);
 }
 
-constexpr int IT_STEP_BYTES = 128;                 // mask bytes per wave step: a lane owns 16 pixels (two bytes)
-constexpr int IT_CHUNK_STEPS = 16;                 // wave steps whose mask bytes are staged in LDS at a time
-constexpr int IT_QUEUE = 64 + IT_STEP_BYTES * 8;   // queue entries (16 bits each): carry (< 64) + one wave step
-constexpr int IT_STAGE_BYTES = IT_CHUNK_STEPS * IT_STEP_BYTES;
-constexpr int IT_WAVE_LDS_BYTES = IT_QUEUE * 2 + IT_STAGE_BYTES;      // per wave: the queue, then the staged mask bytes (4224)
 static_assert(IT_WAVE_LDS_BYTES % 16 == 0 && (IT_QUEUE * 2) % 16 == 0, "the stage is written by LDS-DMA");
 
 // `fd`: M carries the bits of -1.0 / m (IEEE double, computed on the host) instead of the Barrett constant.

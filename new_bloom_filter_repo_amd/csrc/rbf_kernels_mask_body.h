@@ -1,4 +1,4 @@
-// rbf_kernels_mask_body.h -- the body of the two GOP mask kernels (k_residual_mask_gop, k_residual_mask_any_gop in rbf_kernels_lds.h).
+// rbf_kernels_mask_body.h -- the body of the two GOP mask kernels (k_residual_mask_gop, k_residual_mask_any_gop in rbf_kernels_mask.h).
 // NOT a header: it is #included INSIDE each kernel's braces, so that both kernels are ONE function each, compiled from the same text --
 // the luma kernels' instructions stay exactly what they were before the all-channel twin existed (a force-inlined shared __device__ body
 // changed their scheduling).  The including kernel defines SAMPLE, PIXEL_BYTES, NT, THR0 and ANY (template parameters or constexpr
@@ -78,7 +78,10 @@
             const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tot, 63);
             const uint32_t slot = (f - 1u - base) >> 1;                               // < 64 (scalar: f and base are uniform)
             uint32_t keep;
-            // v_writelane takes ONE SGPR over the constant bus, so the lane select rides in M0 (reserved: saved and restored, as RowDmaC does)
+            // v_writelane takes ONE SGPR over the constant bus, so the lane select rides in M0 (reserved: saved and restored, as RowDmaC does).
+            // Hazard: v_writelane must not read an SGPR that a VALU instruction (v_readlane, a ballot) wrote in the last 5 wait states -- it
+            // would see the PREVIOUS value, and hipcc pads no hazards inside asm (the parity tests caught exactly that).  `t` is such an
+            // SGPR: the two s_mov and the s_nop in front of the v_writelane are its distance, do not thin them out.
             asm volatile("s_mov_b32 %1, m0\n\t"
                          "s_mov_b32 m0, %3\n\t"
                          "s_nop 0\n\t"

@@ -1,6 +1,6 @@
-// rbf_kernels_u64.h -- k_query_u64: round 4's frames-inner FP64 query kernel (filters of 2^15 <= m < 2^23 bits that fit LDS twice:
-// BASELINE config 2).  Same outputs and the same arithmetic as k_query_s64 (rbf_kernels_s64.h; reference semantics
-// improved_video_compressor.py:116-138, :245-253) -- the frame pass itself IS k_query_s64's (frame_pass_rows / frame_pass_plain).
+// rbf_kernels_query_f64.h -- k_query_u64 / k_query_u64w: the frames-inner FP64 query kernel (filters of 2^15 <= m < 2^23 bits that fit LDS twice:
+// BASELINE config 2).  Outputs: pass bytes in numpy.packbits order + per-segment pass counts (reference semantics
+// improved_video_compressor.py:116-138, :245-253); the frame pass itself is rbf_query_f64_pass.h (frame_pass_rows / frame_pass_plain).
 // What is new is everything AROUND the pass.  Round 3's stamps showed a wave spending 45 % of a frame outside the pass, and the
 // disassembly showed why: ~75 scalar and ~50 vector instructions per wave and frame of loop head (next geometry -> SGPRs, the
 // stager's address arithmetic, a switch over floor(k*)) and of deferred outputs (four ballots, scalar adds, two 64-bit address
@@ -16,58 +16,21 @@
 //     the kernel runs one loop per class: no switch inside the frame loop.
 //  3. THE NEXT IMAGE RIDES IN BY LDS-DMA (global_load_lds_dwordx4), all five pieces of a wave issued at the top of the pass and
 //     waited for once, in front of the next barrier: no register slots (the kernel drops from 119 to 111 VGPRs), no ds_write
-//     instructions, no load a pass waits for.  Round 2's LDS-DMA kernel (k_query_f64) lost against register staging; in THIS loop it
+//     instructions, no load a pass waits for.  Round 2's LDS-DMA kernel (git history) lost against register staging; in THIS loop it
 //     wins 6 us per launch (profiles/r04_query_u64.txt).  Every row is staged at the batch's row pitch (the rows are padded to it
 //     anyway), so offsets and the lane mask of the last piece are launch constants.
 //  4. Pass counts: a lane adds popc(verdict byte) of two consecutive frames into one packed register; every second frame ONE
 //     six-step DPP reduction yields both wave totals in lane 63, which stores them.  No ballots, no scalar adds.
 //  5. Outputs are addressed as base + 32-bit offset (one v_lshl_add per store) from the output row in the record.
 #pragma once
-#include "rbf_kernels_s64.h"
-#include <algorithm>
-#include <cstring>
+#include "rbf_f64_common.h"
+#include "rbf_kernels.h"
+#include "rbf_lds_dma.h"
+#include "rbf_query_f64_pass.h"
+
 #include <type_traits>
 
 namespace rbf {
-
-constexpr uint32_t U64_REC_BYTES = 32;
-__host__ __device__ constexpr uint32_t u64_geo_bytes(uint32_t nactive) { return (nactive + 1u) * U64_REC_BYTES; }   // LDS behind the two image buffers: one record per coded frame + 1
-constexpr int U64_CLASSES = 6;                                    // floor(k*) = 1, 2, 3, 4, 5 in rows, then everything else (plain pass)
-
-struct U64Classes { uint32_t n[U64_CLASSES]; };                  // coded frames per class, in the order of the compacted table
-
-// Host: the FrameTable k_query_u64 reads (see the kernel) from the batch's plain table (m, floor_k, T per frame; m == 0: not coded).
-__host__ inline FrameTable query_table_u64(const FrameTable &tab, uint32_t nframes, uint32_t *nactive, U64Classes *cls, uint64_t (&empty)[2])
-{
-    FrameTable q;
-    memset(&q, 0, sizeof q);
-    memset(cls, 0, sizeof *cls);
-    empty[0] = empty[1] = 0;
-    uint64_t sorted[MAX_BATCH];
-    uint32_t coded = 0;
-    for (uint32_t f = 0; f < nframes; ++f) {
-        if (tab.f[f].m) sorted[coded++] = tab.f[f].T;
-        else empty[f >> 6] |= 1ull << (f & 63);
-    }
-    std::sort(sorted, sorted + coded);
-    uint32_t j = 0;
-    for (int k = 0; k < U64_CLASSES; ++k)
-        for (uint32_t f = 0; f < nframes; ++f) {
-            if (!tab.f[f].m) continue;
-            const uint32_t fk = tab.f[f].floor_k;
-            const int kf = fk >= 1u && fk <= 5u ? (int)fk - 1 : 5;
-            if (kf != k) continue;
-            const double ninv = -1.0 / (double)tab.f[f].m;
-            q.f[j].m = tab.f[f].m;
-            memcpy(&q.f[j].M, &ninv, 8);
-            q.f[j].floor_k = (fk & 0xFFu) | ((uint32_t)(std::lower_bound(sorted, sorted + coded, tab.f[f].T) - sorted) << 8) | (f << 16);
-            q.f[j].T = sorted[j];
-            ++cls->n[k];
-            ++j;
-        }
-    *nactive = coded;
-    return q;
-}
 
 // Next frame's image -> the other LDS buffer by LDS-DMA (global_load_lds_dwordx4: a lane's 16 bytes land at M0 + lane * 16): no
 // register slots, no ds_write, nothing of the pass waits for a load -- all five 16 KiB piece rows of a workgroup (a wave: 1 KiB of
@@ -130,7 +93,7 @@ struct RowDmaC {
 
 // (the pass counts of two frames are summed over the wave as a packed pair of 16-bit counts, each total <= 512: wave_sum_to_lane63)
 
-// FrameTable as this kernel reads it (host: query_table_u64, rbf_api.hip) -- COMPACTED over the coded frames and ORDERED BY CLASS
+// FrameTable as this kernel reads it (host: query_table, rbf_plan.h) -- COMPACTED over the coded frames and ORDERED BY CLASS
 // (floor(k*) = 1, 2, 3, 4, 5, then the rest):
 //   f[j].m, f[j].M = bits of -1.0 / m        of the j-th coded frame of that order,
 //   f[j].floor_k = floor(k*) | c << 8 | frame index << 16        (c = coded thresholds below the frame's own),
@@ -138,7 +101,7 @@ struct RowDmaC {
 // `cls.n[k]`: frames of class k.  `empty_lo / empty_hi`: bit f set = frame f of the batch is not coded and this launch writes its
 // (empty) outputs.  Dynamic LDS: two image buffers of ((fwords_max + 3) & ~3) + 4 dwords, then u64_geo_bytes(nactive).
 // `image_stride_words32` is also what is staged per frame: rows must be readable over their whole pitch (the library's are).
-// (The measurement variants of this body -- no staging, no barrier, no outputs, no priorities -- were tools/legacy/rbf_kernels_u64_ab.h up to round 4: git history.)
+// (The measurement variants of this body -- no staging, no barrier, no outputs, no priorities -- are in the git history, up to round 4.)
 template <bool WIDE>
 __device__ __forceinline__ void query_u64_body(
     uint64_t n, uint32_t nactive, const FrameTable &tab, const U64Classes &cls, Seeds seeds,
@@ -158,7 +121,10 @@ __device__ __forceinline__ void query_u64_body(
     FrameDev fd_mine{};
     if (threadIdx.x < 2u * MAX_BATCH) fd_mine = tab.f[threadIdx.x < nactive ? threadIdx.x : 0u];
 
-    // ---- frame-independent part (as k_query_s64): hashes of my 8 consecutive pixel indices as (double, low dword), activation ranks
+    // ---- frame-independent part: hashes of my 8 consecutive pixel indices as (double, low dword), activation ranks.
+    // (Twins of three blocks here -- the 8-pixel hash block, the threshold rank search, the frames that are not coded -- are in k_query_s64t,
+    // rbf_kernels_query_f64_tiled.h, and the first and last in k_query_lds, rbf_kernels_barrett.h.  The one real difference: this copy
+    // stores the hash table, k_query_s64t pins hd1 / hd2 with an empty asm.  Kept apart: sharing them changes the ISA of both kernels.)
     static_assert(QL_P == 8, "a lane's verdicts fill one byte");
     double hd1[QL_P], hd2[QL_P];
     uint32_t hl1[QL_P], hl2[QL_P];

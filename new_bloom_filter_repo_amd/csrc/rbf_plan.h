@@ -1,9 +1,9 @@
-// rbf_plan.h -- which kernels serve a batch, and with what geometry.  Pure host code: no context, no HIP runtime call, so
-// tests/c/plan_cases.cpp runs it on a machine without a GPU (tests/test_plan_cpu.py pins the measured crossovers below).
+// rbf_plan.h -- which kernels serve a batch, with what geometry, and the frame tables they read.  Pure host code over rbf_geometry.h
+// and the C ABI's types: no HIP header, no context, so tests/c/plan_cases.cpp is built with a plain host compiler and runs on a machine
+// without a GPU (tests/test_plan_cpu.py pins the measured crossovers below and the query tables).
 #pragma once
 #include "../../include/rbf.h"
-#include "rbf_kernels_i64.h"
-#include "rbf_kernels_u64.h"
+#include "rbf_geometry.h"
 
 #include <algorithm>
 #include <cstring>
@@ -64,13 +64,18 @@ static int fill_table(const rbf_filter_params *params, uint32_t count, FrameTabl
     return RBF_OK;
 }
 
-// The FrameTable k_query_s64t reads (rbf_kernels_s64.h): COMPACTED over the coded frames -- entry j = j-th coded frame: m, M = bits of
-// -1/m, floor_k = floor(k*) | c << 8 | frame index << 16 (c = coded thresholds below the frame's own), T = j-th smallest threshold.
-// `empty`: bit f = frame f is not coded.
-static FrameTable query_table_s64(const FrameTable &tab, uint32_t nframes, uint32_t *nactive, uint64_t (&empty)[2])
+// The FrameTable the FP64 query kernels read (k_query_u64, rbf_kernels_query_f64.h; k_query_s64t, rbf_kernels_query_f64_tiled.h), from
+// the batch's plain table as fill_table leaves it (m, floor_k, T per frame; m == 0: not coded).  COMPACTED over the coded frames
+// -- entry j: m, M = bits of -1.0 / m and floor_k = floor(k*) | c << 8 | frame index << 16 of the j-th coded frame (c = coded
+// thresholds below the frame's own); T = j-th smallest threshold of the coded frames (the thresholds are only searched, so they need
+// not follow the frames' order).
+// `cls` non-null (k_query_u64): the coded frames are ORDERED BY CLASS of floor(k*) -- 1, 2, 3, 4, 5, then everything else -- and
+// cls->n[k] counts class k; null (k_query_s64t): they keep the batch's order.  `empty`: bit f = frame f is not coded.
+static FrameTable query_table(const FrameTable &tab, uint32_t nframes, U64Classes *cls, uint32_t *nactive, uint64_t (&empty)[2])
 {
     FrameTable q;
     memset(&q, 0, sizeof q);
+    if (cls) memset(cls, 0, sizeof *cls);
     empty[0] = empty[1] = 0;
     uint64_t sorted[MAX_BATCH];
     uint32_t coded = 0;
@@ -80,16 +85,20 @@ static FrameTable query_table_s64(const FrameTable &tab, uint32_t nframes, uint3
     }
     std::sort(sorted, sorted + coded);
     uint32_t j = 0;
-    for (uint32_t f = 0; f < nframes; ++f) {
-        if (!tab.f[f].m) continue;
-        const double ninv = -1.0 / (double)tab.f[f].m;
-        const uint32_t below = (uint32_t)(std::lower_bound(sorted, sorted + coded, tab.f[f].T) - sorted);
-        q.f[j].m = tab.f[f].m;
-        memcpy(&q.f[j].M, &ninv, 8);
-        q.f[j].floor_k = tab.f[f].floor_k | (below << 8) | (f << 16);
-        q.f[j].T = sorted[j];
-        ++j;
-    }
+    for (int k = 0; k < (cls ? U64_CLASSES : 1); ++k)
+        for (uint32_t f = 0; f < nframes; ++f) {
+            if (!tab.f[f].m) continue;
+            const uint32_t fk = tab.f[f].floor_k;
+            if (cls && (fk >= 1u && fk <= 5u ? (int)fk - 1 : 5) != k) continue;
+            const double ninv = -1.0 / (double)tab.f[f].m;
+            const uint32_t below = (uint32_t)(std::lower_bound(sorted, sorted + coded, tab.f[f].T) - sorted);
+            q.f[j].m = tab.f[f].m;
+            memcpy(&q.f[j].M, &ninv, 8);
+            q.f[j].floor_k = (fk & 0xFFu) | (below << 8) | (f << 16);
+            q.f[j].T = sorted[j];
+            if (cls) ++cls->n[k];
+            ++j;
+        }
     *nactive = coded;
     return q;
 }
@@ -106,7 +115,7 @@ constexpr size_t LDS_LIMIT = 160 * 1024;
 // profiles/r04_bigtable.txt)
 constexpr size_t HASH_TABLE_CACHE_BYTES = (size_t)96 << 20;
 constexpr uint32_t MAX_INSERT_TILES = 7, MAX_QUERY_TILES = 3;     // measured crossovers, see plan_insert_tiles
-// pixels x coded frames of a launch from which its one-shot data is moved with non-temporal accesses (rbf_kernels_lds.h, cache-policy
+// pixels x coded frames of a launch from which its one-shot data is moved with non-temporal accesses (rbf_lds_dma.h, cache-policy
 // note): 1080p from 64 frames, 2160p from 16
 constexpr uint64_t STREAM_MIN_PIXEL_FRAMES = 64ull * 1920 * 1080;
 
@@ -175,7 +184,7 @@ static BatchSizes classify(const rbf_filter_params *params, uint32_t nframes)
 // Tiling re-hashes (insert) / re-probes (query) every key once per tile, so its cost grows with the
 // tile count while the global-memory kernels' does not.  Measured ps per (pixel, frame), 4K..16K frames:
 // insert tiled 3.1 / 5.2 / 6.3 / 10.4 at 3 / 5 / 7 / 10 tiles vs 7.8 generic; query tiled 5.8 / 11.2 at
-// 2 / 4 tiles vs 8.1-9.0 generic (profiles/r01_large_frames.txt).  Past the crossover the generic kernels run
+// 2 / 4 tiles vs 8.1-9.0 generic (round 1's large-frame runs: git history).  Past the crossover the generic kernels run
 // (16K frames: 59 instead of 9 Gpixel/s).
 static void plan_insert_tiles(Plan &p, const Knobs &k, const BatchSizes &b, bool have_ones)
 {

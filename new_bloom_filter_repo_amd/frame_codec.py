@@ -28,7 +28,7 @@ class _PlaneDict(dict):
     """yuv_info of a YUVFrame: 'format' is there from the start, a plane ('y_plane', 'u_plane', 'v_plane') is copied out of the
     interleaved frame the first time it is asked for (the reference copies all three when it wraps a frame,
     fixed_video_compressor.py:292-296; only the keyframe record ever reads them, :64-75 -- three strided 2 MB copies per 1080p frame were
-    most of what compress_video / decompress_video cost on the host, profiles/r05_e2e.txt)."""
+    most of what compress_video / decompress_video cost on the host: round 5's end-to-end profile, git history)."""
     _CHANNEL = {"y_plane": 0, "u_plane": 1, "v_plane": 2}
 
     def __init__(self, frame):

@@ -1,4 +1,4 @@
-/* Host restatement of mod_m_f64 (csrc/rbf_kernels_lds.h): h mod m through one FP64 fma + one 24-bit multiply-add,
+/* Host restatement of mod_m_f64 (csrc/rbf_f64_common.h): h mod m through one FP64 fma + one 24-bit multiply-add,
  * for 2^15 <= m < 2^23.  Every step below is the C twin of one gfx950 instruction:
  *   hd  = (double)h                      v_cvt_f64_u32 x2, v_ldexp_f64, v_add_f64  (round to nearest)
  *   t   = fma(hd, -1/m, 1.5 * 2^52)      v_fma_f64        (IEEE, round to nearest even)

@@ -277,8 +277,8 @@ def test_fp64_reduction_is_exact(tmp_path):
 
 def test_activation_rank_is_equivalent_to_the_threshold_compare():
     """The FP64 query kernels keep, per pixel, rank = #{coded thresholds t_j <= h_act} (one byte) instead of the 64-bit activation hash,
-    and test rank <= c_f with c_f = #{t_j < T_f} (rbf_kernels_s64.h, rbf_kernels_u64.h; the host side is query_table_s64() in rbf_plan.h
-    and query_table_u64() in rbf_kernels_u64.h).  Restated
+    and test rank <= c_f with c_f = #{t_j < T_f} (rbf_kernels_query_f64.h, rbf_kernels_query_f64_tiled.h; the host side is query_table()
+    in rbf_plan.h).  Restated
     here in Python integers: for any multiset of thresholds -- repeated values, 0, 2^64 - 1 -- and any hash,
     (h_act < T_f) == (rank <= c_f) for every frame f."""
     import bisect

@@ -8,7 +8,7 @@
 //   cycles per wave-instruction per SIMD = launch time x shader clock x (CUs x 4) / (wave-instructions of the launch)
 //
 // with the shader clock taken from s_memtime against the 100 MHz wall clock inside the same launch.  Every opcode goes through inline
-// asm (nothing folds), 8 independent chains per wave.  Mixed rows replay the instruction mix of k_query_s64's reductions and steps.
+// asm (nothing folds), 8 independent chains per wave.  Mixed rows replay the instruction mix of the FP64 frame pass's reductions and steps (csrc/rbf_query_f64_pass.h).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -o build/opbench2 tools/opbench2.hip ; run: ./build/opbench2 > profiles/r04_opbench2.txt
 #include <hip/hip_runtime.h>
@@ -25,7 +25,7 @@ enum Op {
     ADD_VV, ADD_VS, ADD_VK, SUB_VV, XOR_VV, AND_VV, MIN_VV, MIN_VS, LSHR_VS, LSHR_VK, LSHL_VV, LSHL_ADD, LSHL_OR, ADD3, ALIGNBIT, BFE, AND_OR, PERM, BITOP3,
     MUL_LO, MUL_HI, MAD24, MAD_U64, FMA_F32, PK_FMA_F32, FMA_F64, ADD_F64, CVT_F64_U32, CMP_VCC, CMP_SGPR, CMP_SDWA_SGPR, CNDMASK_SGPR, CNDMASK_VCC,
     MOV, MOV_DPP, READLANE, READFIRSTLANE, MBCNT, SALU_ADD,
-    MIX_REDUCE,        // v_fma_f64, v_mad_u64_u32, v_add_u32, v_min_u32: one FP64 reduction of k_query_s64 (rows_reduce4)
+    MIX_REDUCE,        // v_fma_f64, v_mad_u64_u32, v_add_u32, v_min_u32: one FP64 reduction of the frame pass (rows_reduce4)
     MIX_STEP,          // v_lshrrev, v_add, v_lshl_add, v_sub, v_min: one probe step of frame_pass_rows
     MIX_COMBINE,       // v_and, v_lshlrev, v_or (what the compiler makes of  f = (w << (p & 31)) | f ), v_alignbit every third
     MIX_VALU_SALU,     // v_add_u32 + s_add_u32 alternating: does scalar work take VALU issue slots?
