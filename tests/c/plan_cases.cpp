@@ -6,6 +6,12 @@
 //   table: "table by_class full nframes", then one line "m floor_k T" per frame
 // prints what query_table returns for that batch: nactive, the class counts (by_class = 1), the `empty` bits, with full = 1 every
 // coded entry as m:M:floor_k:T (hex), and always the 64-bit FNV-1a of the table's bytes.
+//   sweep: "sweep n nframes cus flags have_ones lo hi step [coded]" (the first `coded` frames, default all, have a filter of m bits,
+// the others none: the batch rbf_encode_gop submits for a GOP whose later pairs did not change)
+// walks m = lo, lo + step, ... up to hi and, wherever the decision differs between two samples, every m in between: one line
+// "transition last=M first=M+1 before=D after=D" per change.  D is the `decision` field every plan line carries too -- what the launch
+// code (rbf_api.hip) reads to choose kernels and tile counts, see decision() -- next to query_tiles and the dynamic LDS the host would
+// launch the query with (launch_query_lds; insert_lds is the insert kernels').  tests/test_plan_boundaries_cpu.py
 #include "../../new_bloom_filter_repo_amd/csrc/rbf_plan.h"
 
 #include <cstdio>
@@ -13,14 +19,80 @@
 
 static int fail(int code, const char *, ...) { return code; }
 
+// tiles the query kernel walks: the tiled kernels' count, 1 for a whole filter in LDS, 0 for the global-memory kernel
+static uint32_t query_tiles(const Plan &p)
+{
+    if (p.query == QueryKind::LdsWhole) return 1;
+    if (p.query == QueryKind::Generic) return 0;
+    return (p.fwords_max + p.query_tile_words - 1) / p.query_tile_words;
+}
+
+// bytes of dynamic LDS launch_query (rbf_api.hip) passes for a batch of `coded` coded frames
+static size_t launch_query_lds(const Plan &p, uint32_t coded)
+{
+    if (p.query == QueryKind::LdsTiledF64) return s64t_lds_bytes(p.query_tile_words);
+    if (p.reads_probe_image()) return p.query_lds_bytes + u64_geo_bytes(coded);
+    return p.query == QueryKind::Generic ? 0 : p.query_lds_bytes;
+}
+
+// The plan as the launch code reads it: fast_insert.query.double_buffer.insert_tab.two_phase.probe_image.insert_tiles.query_tiles.
+// Fields nothing reads in that state are 0: double_buffer outside k_query_lds (k_query_u64 always has two buffers, the tiled kernels
+// one), the insert's tile count and kernel choice when k_insert runs.
+static void decision(const Plan &p, char (&out)[64])
+{
+    const bool lds_barrett = p.query == QueryKind::LdsWhole && !p.reads_probe_image();
+    snprintf(out, sizeof out, "%d.%d.%d.%d.%d.%d.%u.%u", p.fast_insert, (int)p.query, lds_barrett && p.double_buffer, p.insert_tab,
+             p.insert_two_phase, p.reads_probe_image(), p.fast_insert ? p.insert_tiles : 0u, query_tiles(p));
+}
+
+static int sweep(const char *line)
+{
+    unsigned long long n;
+    unsigned nframes, cus, have_ones, lo, hi, step, coded;
+    int flags;
+    const int got = sscanf(line, "sweep %llu %u %u %d %u %u %u %u %u", &n, &nframes, &cus, &flags, &have_ones, &lo, &hi, &step, &coded);
+    if (got < 8 || nframes < 1 || nframes > (unsigned)MAX_BATCH || step < 1 || lo > hi) return 2;
+    if (got < 9) coded = nframes;
+    if (coded < 1 || coded > nframes) return 2;
+    Knobs k;
+    k.set_flags(flags);
+    std::vector<rbf_filter_params> params(nframes);
+    auto decide = [&](uint32_t m, char (&out)[64]) {
+        for (unsigned f = 0; f < nframes; ++f) params[f] = rbf_filter_params{f < coded ? m : 0u, 1, 0};
+        decision(make_plan(k, cus, params.data(), nframes, n, have_ones != 0), out);
+    };
+    char prev[64], cur[64], a[64], b[64];
+    decide(lo, prev);
+    for (uint64_t m0 = lo; m0 < hi;) {
+        const uint64_t m1 = std::min<uint64_t>(m0 + step, hi);
+        decide((uint32_t)m1, cur);
+        if (strcmp(prev, cur)) {
+            memcpy(a, prev, sizeof a);
+            for (uint64_t m = m0 + 1; m <= m1; ++m) {
+                decide((uint32_t)m, b);
+                if (strcmp(a, b)) printf("transition last=%llu first=%llu before=%s after=%s\n", (unsigned long long)(m - 1), (unsigned long long)m, a, b);
+                memcpy(a, b, sizeof a);
+            }
+        }
+        memcpy(prev, cur, sizeof prev);
+        m0 = m1;
+    }
+    printf("swept lo=%u hi=%u step=%u\n", lo, hi, step);
+    return 0;
+}
+
 static void show(const char *tag, const Plan &p, uint32_t nframes)
 {
+    char d[64];
+    decision(p, d);
+    uint32_t coded = 0;
+    for (uint32_t f = 0; f < (uint32_t)MAX_BATCH; ++f) coded += p.slices.n[f] != 0;
     printf("%s fast_insert=%d query=%d double_buffer=%d small_m=%d insert_tab=%d two_phase=%d f64_mod=%d probe_image=%d fwords_max=%u S=%u "
            "per_tile=%u insert_group=%u insert_tile_words=%u insert_tiles=%u query_tile_words=%u insert_lds=%zu query_lds=%zu nseg=%llu "
-           "words_per_seg=%u image_stride=%u slices=",
+           "words_per_seg=%u image_stride=%u decision=%s query_tiles=%u launch_query_lds=%zu lds_limit=%zu slices=",
            tag, p.fast_insert, (int)p.query, p.double_buffer, p.small_m, p.insert_tab, p.insert_two_phase, p.f64_mod, p.reads_probe_image(),
            p.fwords_max, p.S, p.per_tile, p.insert_group, p.insert_tile_words, p.insert_tiles, p.query_tile_words, p.insert_lds_bytes,
-           p.query_lds_bytes, (unsigned long long)p.nseg, p.words_per_seg, p.image_stride_words);
+           p.query_lds_bytes, (unsigned long long)p.nseg, p.words_per_seg, p.image_stride_words, d, query_tiles(p), launch_query_lds(p, coded), LDS_LIMIT);
     for (uint32_t f = 0; f < (uint32_t)MAX_BATCH; ++f)
         if (f < nframes || p.slices.n[f]) printf("%x,", p.slices.n[f]);
     printf("\n");
@@ -57,6 +129,10 @@ int main()
     while (fgets(line, sizeof line, stdin)) {
         if (!strncmp(line, "table", 5)) {
             if (int r = show_table(line)) return r;
+            continue;
+        }
+        if (!strncmp(line, "sweep", 5)) {
+            if (int r = sweep(line)) return r;
             continue;
         }
         unsigned long long n;

@@ -227,8 +227,8 @@ def test_adversarial_filter_lengths(eng, oracle):
 
 
 def test_filter_lengths_up_to_the_abi_limit(oracle):
-    """m beyond 2^30 (where the small-m reduction no longer applies) up to the ABI limit 2^32 - 1:
-    set bits, witness and round trip against positions computed with the oracle's primitives (a
+    """m on both sides of 2^30 (the last m of the small-m reduction and the first without it: tests/plan_boundaries.py, SMALL_M_END)
+    and beyond, up to the ABI limit 2^32 - 1: set bits, witness and round trip against positions computed with the oracle's primitives (a
     byte-per-bit oracle filter of 4 Gbit would not fit the host)."""
     import math
     ctx = nat.Context(0)
@@ -236,7 +236,7 @@ def test_filter_lengths_up_to_the_abi_limit(oracle):
     n = 2000
     mask = make_mask(99, n, 0.15)
     s1, s2, sa = P.SEEDS_VIDEO
-    for m, k in (((1 << 30) + 7, 2.3), ((1 << 31) + 11, 1.5), ((1 << 32) - 1, 3.25)):
+    for m, k in ((1 << 30, 2.3), ((1 << 30) + 1, 2.3), ((1 << 30) + 7, 2.3), ((1 << 31) + 11, 1.5), ((1 << 32) - 1, 3.25)):
         fk, pa = math.floor(k), k - math.floor(k)
 
         def positions(i):
