@@ -104,7 +104,8 @@ int rbf_memcpy_d2d(rbf_ctx *ctx, void *dst_dev, const void *src_dev, size_t byte
 #define RBF_K_NOISE   10
 #define RBF_K_PACK    11
 #define RBF_K_HASHTAB 12      /* k_hash_table: the per-batch table of the pixel indices' three hashes */
-#define RBF_K_COUNT   13
+#define RBF_K_HOLD    13      /* k_temporal_hold (+ _px): the near-lossless stage in front of the mask stage */
+#define RBF_K_COUNT   14
 int rbf_timing_enable(rbf_ctx *ctx, int on);
 /* Testing / tuning knob (bit mask).  0 (default) = pick the fastest variant that fits.  Only LIVE alternatives are selectable (ABI 3
  * dropped the bits that picked superseded kernels: 6 and 13 are ignored).
@@ -185,6 +186,28 @@ int rbf_residual_mask_batch_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t fr
                                uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
                                uint32_t sample_bytes, int32_t thr_floor, const int32_t *thr_floors,
                                void *masks_dev, uint64_t mask_stride_bytes, uint64_t *ones_dev, uint32_t mask_channels);
+
+/* ---- A1, near-lossless: bounded-error temporal hold --------------------------------------------- */
+/* In place, on nframes dense interleaved frames (frame f at frames_dev + f*frame_stride_bytes; a frame is width*height pixels of
+ * `channels` samples of sample_bytes, no row padding).  Per pixel and run -- run_starts (HOST array of nframes bytes, NULL = one run):
+ * frame 0 and every frame f with run_starts[f] != 0 start a run, exactly the keyframes rbf_encode_runs_begin takes --
+ *     y_0 = x_0;   y_t = y_{t-1} if |x_t[c] - y_{t-1}[c]| <= max_error for EVERY sample c of the pixel, else y_t = x_t (whole pixel)
+ * and frame t is overwritten with y_t; a run's first frame is never written.  The difference is the true unsigned one (16-bit 0 and
+ * 0x8000 are 32768 apart; no int16 wrap).  The comparison is against the HELD pixel, so the loop is closed: |y_t - x_t| <= max_error
+ * for every sample of every frame, however slowly x drifts, and y_t differs from y_{t-1} exactly where the hold let a pixel through.
+ * Coding the held block with the exact all-channel mask (rbf_encode_runs_begin_ex, mask_channels = channels, the same run_starts) is
+ * therefore a near-lossless codec with a per-sample bound -- what JPEG-LS calls NEAR.  The reference's knob for sensor noise
+ * (noise_tolerance / min_diff_threshold / max_diff_threshold and the thresholded _calculate_frame_diff, improved_video_compressor.py:
+ * 768-847) compares luma only, against the previous INPUT frame (open loop: a drift of one level per frame is never coded), and bounds
+ * nothing.  Idempotent: holding y gives y.  Deterministic (no atomics).  Asynchronous on the context's stream.
+ * Frames whose base and stride are multiples of 16 go through 16-byte accesses, any other sample-aligned layout and the last
+ * (width*height) % 16 pixels of a frame through a per-pixel kernel.
+ * max_error == 0 or nframes < 2: RBF_OK, nothing is launched.  RBF_EINVAL: channels outside 1..4, sample_bytes not 1 or 2,
+ * frames_dev or frame_stride_bytes not a multiple of sample_bytes, frame_stride_bytes < width*height*channels*sample_bytes (with
+ * nframes >= 2).  RBF_ERANGE: max_error >= 2^(8*sample_bytes). */
+int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                           uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                           uint32_t max_error, const uint8_t *run_starts);
 
 /* ---- A1, BGR input  (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY), :794-795) --------------------- */
 /* gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15 per pixel -- OpenCV 4.x's integer path for 8- and

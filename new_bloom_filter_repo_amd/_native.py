@@ -15,8 +15,8 @@ RBF_ENOMEM = -12
 RBF_EIO = -5
 RBF_ERANGE = -34
 
-K_MASK, K_INSERT, K_QUERY, K_STITCH, K_EXPAND, K_GATHER, K_SCATTER, K_INDEX, K_REDUCE, K_SCAN, K_NOISE, K_PACK, K_HASHTAB = range(13)
-KERNEL_NAMES = ["mask", "insert", "query", "stitch", "expand", "gather", "scatter", "index", "reduce", "scan", "noise", "pack", "hashtab"]
+K_MASK, K_INSERT, K_QUERY, K_STITCH, K_EXPAND, K_GATHER, K_SCATTER, K_INDEX, K_REDUCE, K_SCAN, K_NOISE, K_PACK, K_HASHTAB, K_HOLD = range(14)
+KERNEL_NAMES = ["mask", "insert", "query", "stitch", "expand", "gather", "scatter", "index", "reduce", "scan", "noise", "pack", "hashtab", "hold"]
 STATS_PER_FRAME = 4
 PAIR_SKIPPED = 0xFFFFFFFF                 # params[p].floor_k of a pair across a keyframe (rbf_encode_runs)
 OPT_SEPARATE_FINISH, OPT_INSERT_SLICES = 2, 4    # rbf_ctx_option keys (include/rbf.h); keys 1, 3, 5 and 99 of earlier ABIs are gone with what they selected
@@ -74,6 +74,7 @@ _PROTOS = {
     "rbf_encode_gop_finish": (_int, [_vp, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double)]),
     "rbf_residual_mask_batch": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp]),
     "rbf_residual_mask_batch_ex": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp, _u32]),
+    "rbf_temporal_hold_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_record_max_bytes": (_u64, [_u32, _u64]),
     "rbf_pack_records": (_int, [_vp, _u32, _u64, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double),
                                 _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64]),

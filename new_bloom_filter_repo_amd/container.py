@@ -90,3 +90,10 @@ def plan_range(first_index, start, stop, keyframe_interval, block_frames, inter_
         blocks.append((t - 1, end, [u - (t - 1) for u in range(t, end) if is_keyframe(u, first_index, keyframe_interval)]))      # keyframes inside the block: new runs
         t = end
     return fixed, blocks
+
+
+def blocks_off_keyframes(blocks, first_index, keyframe_interval):
+    """The blocks of a plan_range() plan whose first frame -- the one a block reads but does not code -- is NOT a keyframe of the stream.
+    A near-lossless call (max_error > 0) needs this list to be empty: a block's frames are held against the block's own first frame, so a
+    block that starts inside a run would need the held state of the block in front of it, which lives in another lane's coder."""
+    return [b for b in blocks if not is_keyframe(b[0], first_index, keyframe_interval)]

@@ -61,7 +61,8 @@ class GopCoder:
 
     def __init__(self, ctx, width, height, nframes, channels=3, sample_bytes=1, seeds=P.SEEDS_VIDEO,
                  allocator=None, threshold=0.0, out_allocator=None, frames_block=None, adaptive=None,
-                 planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None, mask_channels=1):
+                 planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None, mask_channels=1,
+                 max_error=0):
         """allocator: device memory source (default: library-owned); out_allocator: separate source for
         the output record (filters, witnesses, stats); frames_block: share another coder's frame buffer.
         threshold=None with adaptive=(noise_tolerance, min_thr, max_thr): per-frame noise-adaptive
@@ -76,6 +77,12 @@ class GopCoder:
         `skipped`).  The reference codes frame by frame (improved_video_compressor.py:198-266); batching whole GOPs is this package's.
         mask_channels: 1 (default) = the luma mask; >= 2 = the all-channel mask (rbf_encode_runs_begin_ex): a pixel's bit is 1 when any of
         its first mask_channels samples changed.  Lossless only: threshold 0, no adaptive thresholds, interleaved frames (not planar_luma).
+        max_error: 0 (default) = lossless.  > 0 = near-lossless: encode_begin() first runs the bounded-error temporal hold
+        (rbf_temporal_hold_runs, same run starts) over the resident GOP and then codes the HELD frames exactly, so every decoded sample is
+        within max_error of the original and a run's first frame is exact.  THE RESIDENT BLOCK IS MODIFIED IN PLACE: gather_values() and
+        rice_streams() read the held frames (that is what makes the records consistent), and so does every other coder that shares the
+        block through frames_block.  The hold is idempotent, so encoding a resident GOP again gives the same rows.  Needs a mask that
+        sees every sample (mask_channels == channels, or channels == 1); not with planar_luma, adaptive or a non-zero threshold.
         """
         from .engine import threshold_floor
         self.mask_channels = int(mask_channels)
@@ -88,6 +95,21 @@ class GopCoder:
                 raise ValueError("the all-channel mask is lossless only: no adaptive thresholds")
             if not np.ndim(threshold) == 0 or float(threshold) != 0.0:
                 raise ValueError("the all-channel mask is lossless only: threshold must be 0, got %r" % (threshold,))
+        if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
+            raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
+        self.max_error = int(max_error)
+        if self.max_error:
+            if self.max_error >> (8 * sample_bytes):
+                raise ValueError("max_error %d does not fit a %d-bit sample" % (self.max_error, 8 * sample_bytes))
+            if self.mask_channels != channels:
+                raise ValueError("max_error > 0 holds every sample of a pixel: the mask has to see them all (mask_channels == channels = %d, "
+                                 "got %d)" % (channels, self.mask_channels))
+            if planar_luma:
+                raise ValueError("max_error > 0 holds the interleaved frames: not with planar_luma")
+            if threshold is None or adaptive is not None:
+                raise ValueError("max_error > 0 codes the held frames exactly: no adaptive thresholds")
+            if not np.ndim(threshold) == 0 or float(threshold) != 0.0:
+                raise ValueError("max_error > 0 codes the held frames exactly: threshold must be 0, got %r" % (threshold,))
         self.ctx, self.W, self.H, self.F, self.C, self.sb = ctx, width, height, nframes, channels, sample_bytes
         self.n = width * height
         self.pairs = nframes - 1
@@ -233,6 +255,9 @@ class GopCoder:
             src, fstride, pitch, pstride = self.luma.ptr + gop * self.luma_bytes * self.F, self.luma_bytes, self.W * self.sb, self.sb
         else:
             src, fstride, pitch, pstride = self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.W * self.C * self.sb, self.C * self.sb
+        if self.max_error:                            # near-lossless: the block becomes its held sequence, which is then coded exactly
+            nat.check(nat.lib().rbf_temporal_hold_runs(self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb, self.max_error,
+                                                       self.run_starts))
         nat.check(nat.lib().rbf_encode_runs_begin_ex(
             self.ctx.handle, src, fstride, self.F, self.W, self.H,
             pitch, pstride, self.sb, self.thr, self.thr_tab, self.run_starts, ctypes.byref(self.seeds),

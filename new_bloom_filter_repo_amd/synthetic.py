@@ -86,14 +86,25 @@ def _rgb_to_yuv444(rgb, bits):
     return np.clip(np.rint(np.stack([y, u, v], axis=-1)), 0, top)
 
 
-def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, color_space="YUV"):
+def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, color_space="YUV", sensor_noise=0):
     """nframes (H, W, 3) frames that change the way camera footage does, unlike make_gop: a smooth RGB texture of which a Bernoulli(moving)
     set of pixels is perturbed by a few levels per channel in every pair, then converted to YUV444 (BT.601, rounded) -- so in every pair
     some pixels change in chroma while their luma stays the same (the luma residual mask misses them).  color_space="BGR" returns the RGB
     frames in B, G, R order before the conversion (channel 0 = B: some pixels change in G or R only).  16-bit: the samples are scaled to 16
-    bits over a fixed fine texture, and in every pair a few channel-0 samples change by exactly 0x8000 (the int16 rule's blind spot)."""
+    bits over a fixed fine texture, and in every pair a few channel-0 samples change by exactly 0x8000 (the int16 rule's blind spot).
+    sensor_noise=a > 0: what a sensor adds to all of that -- every emitted sample of every frame carries independent uniform integer noise
+    in [-a, a] (clipped to the sample range; drawn from a generator of its own, so the scene is the one sensor_noise=0 draws up to the
+    jumps), so no two frames share a sample for long and the exact mask is almost all ones.  The moving set then jumps further: all three
+    RGB channels of a moving pixel move the same way by 2a + 8 .. 2a + 14 levels (luma moves as far, short of clipping at the range's
+    ends), which is more than 2a + max_error for every max_error <= 6 -- a near-lossless hold of that bound lets it through; the one pixel
+    per pair whose luma is kept moves as it does without noise.  sensor_noise=0 (default) consumes the same random numbers and returns
+    the same bytes as before the keyword existed."""
     if color_space not in ("YUV", "BGR"):
         raise ValueError("color_space must be 'YUV' or 'BGR'")
+    sensor_noise = int(sensor_noise)
+    if sensor_noise < 0:
+        raise ValueError("sensor_noise must be >= 0")
+    noise_rng = np.random.default_rng([int(seed), 0x5E4501]) if sensor_noise else None
     rng = np.random.default_rng(seed)
     dtype = np.dtype(dtype)
     bits = 8 * dtype.itemsize
@@ -120,6 +131,9 @@ def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, c
         f = np.ascontiguousarray(img[..., ::-1] if color_space == "BGR" else img).astype(dtype)
         if bits == 16:
             f[..., 0] ^= (flip * 0x8000).astype(np.uint16)
+        if sensor_noise:                         # last: the noise sits on what the sensor sees, the 0x8000 offsets included
+            noisy = f.astype(np.int64) + noise_rng.integers(-sensor_noise, sensor_noise + 1, f.shape)
+            f = np.clip(noisy, 0, top).astype(dtype)
         frames.append(f)
     emit(cur)
     n = width * height
@@ -128,7 +142,10 @@ def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, c
         if idx.size == 0:
             idx = rng.integers(0, n, 1)
         ys, xs = np.unravel_index(idx, (height, width))
-        d = rng.integers(-6, 7, (idx.size, 3))
+        if sensor_noise:                                                   # a jump the noise cannot be mistaken for: see the docstring
+            d = rng.integers(2 * sensor_noise + 8, 2 * sensor_noise + 15, (idx.size, 3)) * rng.choice((-1, 1), (idx.size, 1))
+        else:
+            d = rng.integers(-6, 7, (idx.size, 3))
         d[np.all(d == 0, axis=1), 1] = 1                                   # every chosen pixel moves
         d = d * scale
         d[0] = (3, 0, -8) if color_space == "YUV" else (2, -1, 0)          # luma kept, chroma moved -- at least once per pair (BGR: B = RGB[2])

@@ -2,6 +2,7 @@
 verify_lossless  -- FixedVideoCompressor.verify_lossless (fixed_video_compressor.py:217-285)
 verify_bit_exact -- verify_true_lossless.verify_bit_exact (verify_true_lossless.py:338-492),
                     without the OpenCV diagnostic image dumps.
+verify_max_error -- the near-lossless mode's guarantee (ImprovedVideoCompressor(max_error=...)); the reference has no counterpart.
 Unlike the reference (which unwraps with `hasattr(x, 'data')` and then crashes on unequal plain
 ndarrays, whose `.data` is a memoryview) both accept plain ndarrays and YUVFrame wrappers."""
 import numpy as np
@@ -64,3 +65,29 @@ def verify_bit_exact(original_frames, decompressed_frames, color_space="BGR", ve
         print(f"Bit-exact verification: {'SUCCESS' if result['success'] else 'FAILED'}")
         print(f"  Exact frame matches: {exact}/{len(original_frames)}")
     return result
+
+
+def verify_max_error(original_frames, decoded_frames, max_error, keyframe_interval=None):
+    """The near-lossless guarantee: every decoded sample within max_error of the original.  Returns frame_count, max_abs_error (the worst
+    sample, exact integer arithmetic), worst_frame (its index, -1 when every frame is exact), within_bound, and -- when keyframe_interval
+    is given -- keyframes_exact: every frame t with t % keyframe_interval == 0 equals its original.  A frame-count or shape mismatch is
+    not within any bound: within_bound False with a `reason`."""
+    out = {"frame_count": len(original_frames), "max_error": int(max_error), "max_abs_error": 0, "worst_frame": -1, "within_bound": False}
+    if len(original_frames) != len(decoded_frames):
+        out["reason"] = f"Frame count mismatch: {len(original_frames)} vs {len(decoded_frames)}"
+        return out
+    keys_exact = True
+    for i, (o, d) in enumerate(zip(original_frames, decoded_frames)):
+        o, d = _arr(o), _arr(d)
+        if o.shape != d.shape:
+            out["reason"] = f"Shape mismatch in frame {i}: {o.shape} vs {d.shape}"
+            return out
+        worst = int(np.abs(o.astype(np.int64) - d.astype(np.int64)).max()) if o.size else 0
+        if worst > out["max_abs_error"]:
+            out["max_abs_error"], out["worst_frame"] = worst, i
+        if keyframe_interval and i % int(keyframe_interval) == 0 and worst:
+            keys_exact = False
+    out["within_bound"] = out["max_abs_error"] <= int(max_error)
+    if keyframe_interval:
+        out["keyframes_exact"] = keys_exact
+    return out

@@ -25,7 +25,7 @@ import numpy as np
 from . import container
 from . import params as P
 from ._native import frame_geometry
-from .container import INTER, INTER_RICE, KEY, KEY_RICE, KEYS, is_keyframe, plan_range
+from .container import INTER, INTER_RICE, KEY, KEY_RICE, KEYS, blocks_off_keyframes, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
 from .sample_codec import key_format, key_record, parse_key_record, stream_info
 
@@ -65,16 +65,16 @@ class _Lane:
         self.engine = None
         self.samples = None
 
-    def coder(self, W, H, F, C, sb, mask_channels=1):
+    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0):
         from .gop import GopCoder
-        key = (W, H, F, C, sb, mask_channels)
+        key = (W, H, F, C, sb, mask_channels, max_error)
         c = self.coders.get(key)
         if c is None:
             if len(self.coders) >= 2:            # a stream has at most two block sizes (full blocks and its tail)
                 for old in self.coders.values():
                     old.close()
                 self.coders = {}
-            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels)
+            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels, max_error=max_error)
         return c
 
     def decode_engine(self):
@@ -157,8 +157,8 @@ class ImprovedVideoCompressor:
     def __init__(self, noise_tolerance=10.0, keyframe_interval=30, min_diff_threshold=3.0,
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
-                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib"):
-        """Reference signature (improved_video_compressor.py:318-327) plus seven keyword-only extras:
+                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0):
+        """Reference signature (improved_video_compressor.py:318-327) plus eight keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -174,7 +174,26 @@ class ImprovedVideoCompressor:
         compressor decompresses either container.
         sample_codec: "zlib" (default) -- keyframes and changed values in zlib-9, the record formats' own; "rice" -- both through the GPU
         sample codec (sample_codec.py: records 3 and 4, 'BFV2' only, so not with inter_frames=False); frames a type-3 record cannot carry
-        stay zlib keyframes.  decompress_video reads either with any settings."""
+        stay zlib keyframes.  decompress_video reads either with any settings.
+        max_error: 0 (default) -- lossless.  A positive integer -- near-lossless: every decoded sample is within max_error of the original
+        and every keyframe is exact.  Inside a run (a keyframe and the inter-frames that hang off it) a pixel is held at its last coded value
+        while every one of its samples stays within max_error of it, and is updated as a whole otherwise (GopCoder(max_error=...): the
+        bounded-error temporal hold on the GPU); the held frames are then coded exactly, in today's records -- a fresh default compressor
+        decodes the container.  What it buys: on footage with sensor noise the exact mask is almost all ones, the held one is the moving
+        pixels.  Needs mask_channels="all", inter-frames, gop_batching=True, and blocks that start at keyframes (encode_range raises
+        otherwise: block_frames a multiple of keyframe_interval, a range that starts on a keyframe).  A block the GPU cannot batch is
+        coded exactly, which satisfies the bound.  The reference's noise_tolerance / min_diff_threshold / max_diff_threshold stay
+        accepted and unused."""
+        if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
+            raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
+        self.max_error = int(max_error)
+        if self.max_error:
+            if mask_channels != "all":
+                raise ValueError("max_error > 0 holds every sample of a pixel: it needs mask_channels='all'")
+            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
+                raise ValueError("max_error > 0 acts on inter-frames: not with inter_frames=False or keyframe_interval=1")
+            if not gop_batching:
+                raise ValueError("max_error > 0 needs gop_batching=True: the frame-by-frame route has no resident run to hold")
         if mask_channels not in ("luma", "all"):
             raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
         if sample_codec not in ("zlib", "rice"):
@@ -315,7 +334,7 @@ class ImprovedVideoCompressor:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
         mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
-        coder = lane.coder(W, H, len(seg), C, sb, mc)
+        coder = lane.coder(W, H, len(seg), C, sb, mc, self.max_error)
         coder.set_run_starts(list(run_starts))
         block = _as_block(data)
         t1 = time.perf_counter()
@@ -340,8 +359,14 @@ class ImprovedVideoCompressor:
             busy.append((t1, t5))
         n = H * W
         out = []
+        broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
         for f, r in enumerate(res):
-            if r.get("skipped") or int(uncovered[f]):    # the pair in front of a keyframe; or chroma moved where luma did not: not representable
+            if r.get("skipped"):                 # the pair in front of a keyframe
+                broken = False
+                out.append(None)
+                continue
+            if int(uncovered[f]) or broken:      # chroma moved where luma did not: not representable.  With max_error > 0 the rest of the run
+                broken = self.max_error > 0      # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have
                 out.append(None)
                 continue
             p = np.uint64(r["ones"]) / n
@@ -380,6 +405,12 @@ class ImprovedVideoCompressor:
         busy = []
         gpu_keys = set()                         # sample_codec="rice": keyframes coded as type-3 records on the lanes
         fixed_keys, blocks = plan_range(first_index, start, stop, I, self.block_frames, inter_frames)
+        if self.max_error and blocks:
+            off = blocks_off_keyframes(blocks, first_index, I)
+            if off:
+                raise ValueError("max_error=%d: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
+                                 "another block's coder; make block_frames (%d) a multiple of keyframe_interval (%d) and start the range "
+                                 "on a keyframe" % (self.max_error, off[0][0], self.block_frames, I))
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
 
@@ -504,6 +535,8 @@ class ImprovedVideoCompressor:
                    "frames_per_second": len(frames) / elapsed if elapsed > 0 else float("inf"),
                    "keyframes": keyframes, "keyframe_ratio": keyframes / len(frames),
                    "output_path": output_path, "color_space": input_color_space, "overall_ratio": ratio}
+        if self.max_error:
+            results["max_error"] = self.max_error
         if self.verbose:
             print("\\nCompression Results:")
             print(f"Original Size: {original_size / (1024 * 1024):.2f} MB")
