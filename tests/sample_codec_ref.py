@@ -42,8 +42,9 @@ def chunk_costs(u, bits):
     return np.stack([(code_lengths(pad, k, bits) * valid).sum(axis=1) for k in range(bits + 1)], axis=1)
 
 
-def encode(u, bits):
-    """The stream of the values u (each < 2^B) as bytes."""
+def encode(u, bits, ks=None):
+    """The stream of the values u (each < 2^B) as bytes.  ks: one k per chunk, each in [0, B], to write the stream under instead of the
+    cheapest (a legal stream of the format that no encoder of this project produces; the decoders must read it all the same)."""
     u = np.asarray(u, dtype=np.int64).reshape(-1)
     n = u.size
     head = struct.pack("<IB3x", n, bits)
@@ -51,7 +52,12 @@ def encode(u, bits):
         return head
     c = -(-n // CHUNK)
     costs = chunk_costs(u, bits)
-    ks = costs.argmin(axis=1)                    # (argmin: the first, i.e. smallest, k on a tie)
+    if ks is None:
+        ks = costs.argmin(axis=1)                # (argmin: the first, i.e. smallest, k on a tie)
+    else:
+        ks = np.asarray(ks, dtype=np.int64).reshape(-1)
+        if ks.size != c or ks.min() < 0 or ks.max() > bits:
+            raise ValueError("ks: one k in [0, %d] for each of the %d chunks" % (bits, c))
     nbits = costs[np.arange(c), ks]
     words = (nbits + 31) // 32
     hdr = head + ks.astype(np.uint8).tobytes() + words.astype("<u2").tobytes()
@@ -74,6 +80,43 @@ def encode(u, bits):
     acc += np.bincount(w + 1, weights=(wide >> 32).astype(np.float64), minlength=total + 1)       # (disjoint bits: sums are exact)
     assert acc[total] == 0
     return hdr + acc[:total].astype(np.uint64).astype("<u4").tobytes()
+
+
+def values_for_k(bits, k, n, seed, escape_every=0):
+    """n values for which encode picks k in every chunk, k <= B - 2: uniform in [2^(k-1), 2^(k+1)) for k >= 1 (k costs k + 5/3 bits a value,
+    k - 1 and k + 1 cost k + 2), sparse ones for k = 0.  escape_every: every so-manyth value is 2^B - 1 instead (an escape code where
+    (2^B - 1) >> k >= 16).  Not defined for k = B - 1, which no chunk ever picks, nor for k = B (uniform values over the whole range)."""
+    if not 0 <= k <= bits - 2:
+        raise ValueError("values_for_k: k = %d outside [0, %d]" % (k, bits - 2))
+    rng = np.random.default_rng(seed)
+    top = (1 << bits) - 1
+    if k == 0:
+        u = (rng.random(n) < 0.1).astype(np.int64)
+    else:
+        u = np.minimum(rng.integers(1 << (k - 1), 1 << (k + 1), n), top)
+    if escape_every:
+        u[escape_every - 1::escape_every] = top
+    return u
+
+
+ESCAPE_RUNS = 44
+
+
+def escape_offsets(bits):
+    """One chunk of zeros (k = 0: one bit each) with 2^B - 1, an escape code of 16 + B bits, behind runs of 0, 1, 2, ... 43 zeros (990
+    values): the escape codes start at every bit offset 0 .. 31 of a word."""
+    parts = []
+    for run in range(ESCAPE_RUNS):
+        parts.append(np.zeros(run, dtype=np.int64))
+        parts.append(np.array([(1 << bits) - 1], dtype=np.int64))
+    return np.concatenate(parts)
+
+
+def escape_starts(u, k, bits):
+    """The bit position, inside its chunk's payload, of every escape code of the values u of ONE chunk coded under k < B."""
+    u = np.asarray(u, dtype=np.int64).reshape(-1)
+    lens = code_lengths(u, k, bits)
+    return (np.cumsum(lens) - lens)[(u >> k) >= ESC]
 
 
 def decode(buf):

@@ -1,7 +1,10 @@
 """GPU tier of the sample codec (rbf_rice_* / ImprovedVideoCompressor(sample_codec="rice")): the kernels' streams are the numpy
 reference's bytes (tests/sample_codec_ref.py) for arbitrary values, keyframes of every shape and channel count and a GopCoder block's pairs;
 reference bytes decode back on poisoned buffers; bad streams are refused without a fault; and the product surface round trips camera-like
-clips bit-exactly on every route, in containers smaller than the zlib mode's, sharded or not."""
+clips bit-exactly on every route, in containers smaller than the zlib mode's, sharded or not.  The sweep of the kernels' own code paths --
+every Rice parameter, escape codes at every bit offset, hand-built streams under parameters no encoder picks, rbf_rice_encode_inter /
+rbf_rice_apply_inter called directly on ragged and empty streams, and the refusals of rbf_rice_apply_inter -- is
+tests/test_gpu_sample_codec_sweep.py."""
 import ctypes
 import json
 import os

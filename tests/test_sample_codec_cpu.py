@@ -1,6 +1,7 @@
 """CPU tier of the sample codec (ImprovedVideoCompressor(sample_codec="rice")): the format pinned by literal vectors and the numpy
 reference (tests/sample_codec_ref.py), the k tie rule, the scan rebuild of keyframes, the type-3 / type-4 records and containers, the
 keyword's validation, and the new kernels' registers (no scratch, no spills).  No GPU needed."""
+import functools
 import inspect
 import os
 import struct
@@ -158,3 +159,243 @@ def test_sample_codec_kernels_do_not_spill():
         assert hits, (name, sorted(rows))
         for n in hits:
             assert rows[n][2] == "0" and rows[n][3] == "0", (n, rows[n])
+
+
+# ------------------------------------------------------------------ inputs of the device sweep (tests/test_gpu_sample_codec_sweep.py)
+# Proved here, on the reference alone, to hit what they claim: every reachable k, escape codes at every bit offset of a word, and
+# hand-built streams under parameters no encoder picks.
+SWEEP_N = 3 * 1024 + 77
+SWEEP = [(bits, k, every) for bits in (8, 16) for k in range(bits - 1) for every in (0, 131)]
+SWEEP_IDS = ["b%d_k%d_%s" % (b, k, "esc" if e else "plain") for b, k, e in SWEEP]
+FORCED = [(bits, k) for bits in (8, 16) for k in range(bits + 1)]
+FORCED_N = 1024 + 77
+
+
+def table_of(blob, n):
+    """(k, words) of every chunk of a stream of n samples."""
+    c = sc.nchunks(n)
+    return np.frombuffer(blob, np.uint8, c, 8).astype(int), np.frombuffer(blob, "<u2", c, 8 + c).astype(int)
+
+
+def escapes_under(u, k, bits):
+    """How many values of u take the escape code under k."""
+    return 0 if k >= bits else int(((np.asarray(u) >> k) >= ref.ESC).sum())
+
+
+def forced_values(bits, k, n, seed):
+    """Values that fit a chunk written under k (its words stay within ceil(samples * B / 32), the cap every decoder checks) while another
+    k is cheaper: the values that pick k - 1 (k = 0: those that pick 1; k = B: those that pick B - 2) cost k + 1 <= B bits each under k
+    -- for k = B - 1 that is every value below 2^(B-1), at exactly B bits.  Where 2^B - 1 escapes under k and there is room (k <= B - 3),
+    every 131st value is an escape."""
+    j = 1 if k == 0 else min(k - 1, bits - 2)
+    every = 131 if ((1 << bits) - 1) >> k >= ref.ESC and k <= bits - 3 else 0
+    return ref.values_for_k(bits, j, n, seed, escape_every=every)
+
+
+def mixed_stream(bits):
+    """(u, ks): four chunks under k = 0, B, a middle k with escapes, and B - 1 on the ragged tail."""
+    mid = bits // 2 - 1
+    u = np.concatenate([forced_values(bits, 0, 1024, 1), samples("uniform", 1024, bits, 2), forced_values(bits, mid, 1024, 3),
+                        forced_values(bits, bits - 1, 77, 4)])
+    return u, [0, bits, mid, bits - 1]
+
+
+@pytest.mark.parametrize("bits,k,every", SWEEP, ids=SWEEP_IDS)
+def test_values_for_k_pick_k_in_every_chunk(bits, k, every):
+    u = ref.values_for_k(bits, k, SWEEP_N, 100 * bits + k, escape_every=every)
+    assert u.size == SWEEP_N and u.min() >= 0 and u.max() < 1 << bits
+    blob = ref.encode(u, bits)
+    ks, _ = table_of(blob, SWEEP_N)
+    assert set(ks) == {k}, ks
+    claimed = bool(every) and ((1 << bits) - 1) >> k >= ref.ESC          # k <= 3 at 8 bits, k <= 11 at 16 bits
+    assert claimed == (bool(every) and k <= bits - 5)
+    assert (escapes_under(u, k, bits) > 0) == claimed
+    if every:
+        assert int((u == (1 << bits) - 1).sum()) >= SWEEP_N // every
+    assert np.array_equal(ref.decode(blob)[0], u)
+
+
+def test_values_for_k_refuses_the_unreachable_k():
+    for bits in (8, 16):
+        for k in (-1, bits - 1, bits):
+            with pytest.raises(ValueError):
+                ref.values_for_k(bits, k, 10, 0)
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+def test_no_chunk_picks_k_b_minus_1(bits):
+    """k = B - 1 is never the cheapest-then-smallest parameter.  (1) A chunk with a value >= 2^(B-1): under k = B - 1 that value costs
+    q + 1 + k = B + 1 bits and every other one B, more than the B bits a value of k = B, so k = B beats it.  (2) All values below 2^(B-1):
+    k = B - 1 costs exactly B bits a value; under k = B - 2, q <= 1, so a value costs at most B -- no more in total, and the tie goes to the
+    smaller k.  Either way argmin != B - 1; only a hand-built stream carries it."""
+    rng = np.random.default_rng(bits)
+    half, quarter = 1 << (bits - 1), 1 << (bits - 2)
+    chunks = [rng.integers(quarter, half, 1024), rng.integers(0, quarter, 1024), np.full(1024, half - 1), np.full(1024, quarter),
+              np.zeros(1024, dtype=np.int64), np.full(1, half - 1), np.full(77, half - 1)]
+    one_high = rng.integers(0, half, 1024)
+    one_high[500] = half
+    top_high = rng.integers(quarter, half, 1024)
+    top_high[0] = (1 << bits) - 1
+    chunks += [one_high, top_high, np.full(1024, half), np.full(3, half)]
+    for hi in (2, 5, quarter, half, half + 1, 1 << bits):                 # random chunks of every magnitude, full and ragged
+        for n in (1, 7, 1023, 1024):
+            chunks.append(rng.integers(0, hi, n))
+    for t in range(200):
+        k = int(rng.integers(0, bits + 1))
+        chunks.append(np.minimum(rng.geometric(1.0 / (1 << k), int(rng.integers(1, 1025))) - 1, (1 << bits) - 1))
+    for u in chunks:
+        costs = ref.chunk_costs(u, bits)[0]
+        assert costs.argmin() != bits - 1, (u[:8], costs)
+        if u.max() < half:
+            assert costs[bits - 1] == u.size * bits >= costs[bits - 2]
+        else:
+            assert costs[bits - 1] > costs[bits]
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+def test_escape_offsets_start_an_escape_at_every_bit_of_a_word(bits):
+    u = ref.escape_offsets(bits)
+    assert u.size <= 1024 and set(u.tolist()) == {0, (1 << bits) - 1}
+    blob = ref.encode(u, bits)
+    ks, words = table_of(blob, u.size)
+    assert list(ks) == [0]
+    starts = ref.escape_starts(u, 0, bits)
+    assert len(starts) == ref.ESCAPE_RUNS == escapes_under(u, 0, bits)
+    assert {int(s) & 31 for s in starts} == set(range(32))
+    payload = int.from_bytes(blob[sc.header_bytes(u.size):], "little")
+    code = 0xFFFF | ((1 << bits) - 1) << 16
+    for s in starts:                                                       # the positions are those of the stream's own bits
+        assert (payload >> int(s)) & ((1 << (16 + bits)) - 1) == code
+    if bits == 16:                                                         # a 32-bit code on a word of its own, and one that leaves one bit of it
+        assert int(starts[0]) == 0 and words[0] > 1
+        assert any(int(s) & 31 == 31 for s in starts)
+    assert np.array_equal(ref.decode(blob)[0], u)
+
+
+@pytest.mark.parametrize("bits,k", FORCED, ids=["b%d_k%d" % c for c in FORCED])
+def test_forced_k_streams_are_legal_and_decode(bits, k):
+    u = forced_values(bits, k, FORCED_N, 7 * bits + k)
+    blob = ref.encode(u, bits, ks=[k, k])
+    ks, words = table_of(blob, FORCED_N)
+    assert list(ks) == [k, k]
+    for ci, ns in enumerate((1024, 77)):                                   # rice_parse's acceptance cap
+        assert 1 <= words[ci] <= (ns * bits + 31) // 32, (ci, words[ci])
+    assert sc.stream_info(blob) == (FORCED_N, bits, len(blob))
+    assert np.array_equal(ref.decode(blob)[0], u)
+    canon = ref.encode(u, bits)
+    assert k not in table_of(canon, FORCED_N)[0] and canon != blob          # a legal k that is not the cheapest
+    if k == bits - 1:
+        assert u.max() < 1 << (bits - 1)
+    if k <= bits - 5:
+        assert escapes_under(u, k, bits) > 0
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+def test_mixed_k_stream_is_legal_and_decodes(bits):
+    u, ks = mixed_stream(bits)
+    assert u.size == SWEEP_N and len(set(ks)) == 4 and ks[-1] == bits - 1
+    blob = ref.encode(u, bits, ks=ks)
+    got, words = table_of(blob, u.size)
+    assert list(got) == ks
+    for ci in range(4):
+        ns = min(1024, u.size - 1024 * ci)
+        assert 1 <= words[ci] <= (ns * bits + 31) // 32
+    assert escapes_under(u[2048:3072], ks[2], bits) > 0
+    assert np.array_equal(ref.decode(blob)[0], u)
+    assert ref.encode(u, bits) != blob
+
+
+def test_forced_k_arguments_are_checked():
+    u = np.arange(1030)
+    assert ref.encode(u % 200, 8, ks=None) == ref.encode(u % 200, 8)
+    for ks in ([3], [3, 3, 3], [3, 9], [-1, 3]):
+        with pytest.raises(ValueError):
+            ref.encode(u % 200, 8, ks=ks)
+
+
+# ------------------------------------------------------------------ clips of the sweep's direct rbf_rice_encode_inter / rbf_rice_apply_inter calls
+W, H = 67, 33
+NPX = W * H                                                           # 2211: three 1024-pixel segments, 35 live bits in the last mask word
+COUNTS = [0, 0, 1, 256, 341, 342, 1024, 1025, 2211, 0, 0]
+SINGLE = [NPX - 1, 1024, 0]                                            # the lone bit: in the ragged last word, first of a segment, pixel 0
+INTER = [(C, dt) for C in (1, 3, 4) for dt in (np.uint8, np.uint16)]
+INTER_IDS = ["c%d_%s" % (C, np.dtype(dt).name) for C, dt in INTER]
+
+
+def mask_with(count, seed, single):
+    m = np.zeros(NPX, dtype=bool)
+    if count == 1:
+        m[single] = True
+    else:
+        m[np.random.default_rng(seed).choice(NPX, count, replace=False)] = True
+    return m.reshape(H, W)
+
+
+@functools.lru_cache(maxsize=None)
+def clip(C, dtype):
+    """(frames, masks, packed masks, reference streams) of 12 frames: frame t differs from frame t-1 at mask t-1's pixels only, by small
+    steps in even pairs (small k) and to fresh uniform samples in odd ones (k = B).  Computed once; the tests leave it unchanged."""
+    bits = 8 * np.dtype(dtype).itemsize
+    rng = np.random.default_rng(1000 * C + bits)
+    single = SINGLE[(INTER.index((C, dtype))) % 3]
+    frames = [rng.integers(0, 1 << bits, (H, W, C)).astype(dtype)]
+    masks = []
+    for f, count in enumerate(COUNTS):
+        m = mask_with(count, 50 * C + f, single)
+        nxt = frames[-1].copy()
+        if f % 2 == 0:
+            nxt[m] = (nxt[m].astype(np.int64) + rng.integers(-3, 4, (count, C))).astype(dtype)        # (wraps mod 2^B)
+        else:
+            nxt[m] = rng.integers(0, 1 << bits, (count, C)).astype(dtype)
+        masks.append(m)
+        frames.append(nxt)
+    frames = np.stack(frames)
+    frames.setflags(write=False)
+    packed = [np.packbits(m.reshape(-1)) for m in masks]
+    streams = [ref.encode(ref.inter_u(frames[f], frames[f + 1], masks[f], bits), bits) for f in range(len(COUNTS))]
+    return frames, masks, packed, streams
+
+
+def test_the_inter_clips_are_what_they_claim():
+    for C, dt in INTER:
+        frames, masks, _, streams = clip(C, dt)
+        bits = 8 * np.dtype(dt).itemsize
+        assert [int(m.sum()) for m in masks] == COUNTS
+        ns = [sc.stream_info(s)[0] for s in streams]
+        assert ns == [c * C for c in COUNTS]
+        tables = [set(table_of(s, n)[0]) for s, n in zip(streams, ns)]
+        assert bits in tables[7] and max(tables[6]) < bits               # one call mixes parameters
+        for f, m in enumerate(masks):
+            assert np.array_equal(frames[f][~m], frames[f + 1][~m])
+    assert {n for C in (1, 3, 4) for n in (c * C for c in COUNTS)} >= {1023, 1024, 1025, 1026}
+    assert {SINGLE[i % 3] for i in range(len(INTER))} == set(SINGLE)
+    assert sorted({SINGLE[INTER.index((C, np.uint16)) % 3] for C in (1, 3, 4)}) == sorted(SINGLE)
+
+
+@functools.lru_cache(maxsize=None)
+def short_chain(C, dtype):
+    """(frames, packed masks, streams) of a chain of three pairs by small steps (every chunk Rice-coded, k < B); the third stream has
+    several chunks."""
+    bits = 8 * np.dtype(dtype).itemsize
+    rng = np.random.default_rng(77 + C + bits)
+    frames = [rng.integers(0, 1 << bits, (H, W, C)).astype(dtype)]
+    masks = []
+    for count in (300, 1, 1100):
+        m = mask_with(count, 9 * count, 1024)
+        nxt = frames[-1].copy()
+        nxt[m] = (nxt[m].astype(np.int64) + rng.integers(-3, 4, (count, C))).astype(dtype)
+        masks.append(m)
+        frames.append(nxt)
+    frames = np.stack(frames)
+    frames.setflags(write=False)
+    streams = [ref.encode(ref.inter_u(frames[t], frames[t + 1], masks[t], bits), bits) for t in range(3)]
+    return frames, [np.packbits(m.reshape(-1)) for m in masks], streams
+
+
+def test_the_short_chain_is_rice_coded():
+    for C, dt in ((3, np.uint16), (4, np.uint8)):
+        frames, packed, streams = short_chain(C, dt)
+        bits = 8 * np.dtype(dt).itemsize
+        assert [int(np.unpackbits(p)[:NPX].sum()) for p in packed] == [300, 1, 1100]
+        n = sc.stream_info(streams[2])[0]
+        assert n == 1100 * C and sc.nchunks(n) >= 2 and table_of(streams[2], n)[0].max() < bits
