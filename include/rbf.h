@@ -455,6 +455,35 @@ int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stre
                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                          const void *masks_dev, uint64_t mask_stride_bytes, void *frames_dev);
 
+/* ---- integrity: frame digests (no reference counterpart) ------------------------------------------ */
+/* FD1, the digest a container stores per frame so that a decoder can prove, without the originals, that it rebuilt the frames the
+ * encoder coded (record type 5 of 'BFV2' containers: '<B' version = 1 | '<B' algo = 1 | '<H' 0 | '<I' count | count x '<Q' digest |
+ * '<Q' FD1 of all preceding body bytes; only as the last record, count = the frame records in front of it).  A frame's bytes are its dense
+ * C-order (height, width, channels) samples, little-endian.  Arithmetic mod 2^64; P1..P5 are the XXH64 primes:
+ *     round(acc, x) = rotl64(acc + x*P2, 31) * P1
+ *     merge(a, b)   = (a ^ round(0, b)) * P1 + P4
+ *     aval(h)       : h ^= h>>33; h *= P2; h ^= h>>29; h *= P3; h ^= h>>32
+ *     block(w[0..511], seed)          one 4096-byte block, zero-padded, as 512 little-endian u64
+ *       for lane l in 0..63:  acc[l] = seed + P5 + l*P1
+ *       for row r in 0..3, half h in 0..1, every lane l:  acc[l] = round(acc[l], w[128*r + 2*l + h])
+ *       for d in 1,2,4,8,16,32:  for every l that is a multiple of 2d:  acc[l] = merge(acc[l], acc[l+d])
+ *       the block's hash is aval(acc[0])
+ *     FD1(bytes b, L = len(b)):
+ *       while len(b) > 4096:  b = the hashes of b's blocks, block j zero-padded and seeded with j, as '<Q' each
+ *       FD1 = block(b zero-padded to 4096, seed = L)
+ * The layout is a wave's: one wave hashes one block, lane l reads the 16 bytes at 1024*r + 16*l of each row (four coalesced 16-byte
+ * loads), the 64 accumulators fold in six cross-lane steps.  merge is not commutative (swapped lanes, rows, halves and blocks all change
+ * the result) and L in the last seed separates a frame from its zero-extended twin.  FD1 of the empty string is 0x19044D0607DE195D.
+ *
+ * rbf_frame_digest_batch: FD1 of nframes byte ranges [frames_dev + f*frame_stride_bytes, +frame_bytes); digests_dev: nframes uint64
+ * (device), asynchronous on the context's stream; 1 + (number of levels) launches whatever nframes is.  Base and stride multiples of 16:
+ * 16-byte loads; any other layout: a generic path.  Nothing outside the byte ranges is read.  frame_bytes >= 1, frame_stride_bytes >=
+ * frame_bytes unless nframes <= 1 (RBF_EINVAL otherwise); nframes == 0 is a no-op.
+ * rbf_frame_digest_host: the same digest of host memory in plain C++: no GPU, no context. */
+int rbf_frame_digest_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                           uint64_t frame_bytes, uint64_t *digests_dev);
+uint64_t rbf_frame_digest_host(const void *bytes, uint64_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@ _LAZY = {
     "ImprovedVideoCompressor": "video_compressor",
     "verify_lossless": "verify",
     "verify_bit_exact": "verify",
+    "verify_container": "verify",
+    "IntegrityError": "integrity",
     "GopCoder": "gop",
 }
 

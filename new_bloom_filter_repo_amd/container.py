@@ -5,12 +5,15 @@ All-keyframe streams are written exactly as the reference does -- 'BFVC' | <I fr
 (improved_video_compressor.py:398-406) -- so either implementation reads them.  Streams with any other record use magic 'BFV2' and prefix
 every record with a type byte, following the type-byte precedent of VideoFrameCompressor.compress_frame (:1053):
   1 = keyframe (zlib, FixedVideoCompressor), 2 = inter-frame (Bloom record, values in zlib-9),
-  3, 4 = the same two roles with the GPU sample codec in place of zlib-9 (sample_codec.py has their layout).
+  3, 4 = the same two roles with the GPU sample codec in place of zlib-9 (sample_codec.py has their layout),
+  5 = the frame digests of all the records in front of it (integrity.py has the layout): optional, only as the LAST record.  It is no
+      frame: split_trailer takes it off, and everything else in this module sees the frame records only.
 """
 import struct
 
 KEY, INTER, KEY_RICE, INTER_RICE = 1, 2, 3, 4
 KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
+DIGESTS = 5
 
 
 def write(records):
@@ -42,6 +45,24 @@ def parse(blob):
         off += 4 + length
         records.append((KEY, body) if magic == b"BFVC" else (body[0], body[1:]))
     return records
+
+
+def split_trailer(records):
+    """(frame records, digests): the digests of a container's DIGESTS record, one per frame record, or None when it has none.  A plain
+    ValueError -- never an integrity error, which speaks of frames -- when the trailer is not the last record, is there twice, does not
+    cover exactly the frame records in front of it, or is damaged (integrity.parse_trailer)."""
+    at = [i for i, (ty, _) in enumerate(records) if ty == DIGESTS]
+    if not at:
+        return list(records), None
+    if len(at) > 1:
+        raise ValueError("%d digest trailers (records %s): a container has at most one" % (len(at), at))
+    if at[0] != len(records) - 1:
+        raise ValueError("the digest trailer is record %d of %d: it may only be the last" % (at[0], len(records)))
+    from .integrity import parse_trailer
+    digests = parse_trailer(records[-1][1])
+    if len(digests) != len(records) - 1:
+        raise ValueError("the digest trailer covers %d frames, the container holds %d" % (len(digests), len(records) - 1))
+    return list(records[:-1]), digests
 
 
 def check_types(types):

@@ -16,6 +16,7 @@
 #include "rbf_kernels_query_f64_tiled.h"
 #include "rbf_kernels_witness.h"
 #include "rbf_kernels_pack.h"
+#include "rbf_kernels_digest.h"
 #include "rbf_rice_host.h"
 
 #include <cmath>
@@ -1534,6 +1535,55 @@ int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stre
     }
     HIP_TRY(hipGetLastError());
     return RBF_OK;
+}
+
+// ---- integrity: FD1 frame digests (rbf_digest.h, rbf_kernels_digest.h)
+int rbf_frame_digest_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                           uint64_t frame_bytes, uint64_t *digests_dev)
+{
+    if (int r = set_device(ctx)) return r;
+    if (nframes == 0) return RBF_OK;
+    if (frame_bytes == 0) return fail(RBF_EINVAL, "frame_bytes must be >= 1: an empty frame has no resident bytes to hash");
+    if (!frames_dev || !digests_dev) return fail(RBF_EINVAL, "null device pointer");
+    if ((uintptr_t)digests_dev % 8) return fail(RBF_EINVAL, "digests_dev must be 8-byte aligned");
+    if (nframes > 1 && frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    const uint32_t levels = fd1_levels(frame_bytes);
+    const uint64_t words = fd1_scratch_words(frame_bytes);
+    constexpr uint32_t MAX_Y = 65535;                             // frames of one launch (gridDim.y)
+    if (int r = ctx->digest_lvl.reserve((size_t)(nframes < MAX_Y ? nframes : MAX_Y) * words * 8)) return r;
+    for (uint32_t f0 = 0; f0 < nframes; f0 += MAX_Y) {
+        const uint32_t cnt = nframes - f0 < MAX_Y ? nframes - f0 : MAX_Y;
+        const uint8_t *src = (const uint8_t *)frames_dev + (uint64_t)f0 * frame_stride_bytes;
+        uint64_t stride = frame_stride_bytes, len = frame_bytes;
+        uint64_t *lvl = ctx->digest_lvl.p;                        // level k's hashes: cnt rows of fd1_blocks(len of level k) words
+        for (uint32_t k = 0; k <= levels; ++k) {
+            const bool top = k == levels;
+            const uint64_t nb = fd1_blocks(len);
+            uint64_t *dst = top ? digests_dev + f0 : lvl;
+            const uint64_t dst_stride = top ? 1 : nb;
+            // frames: 16-byte loads where base and stride allow them; the arrays of block hashes are 8-byte aligned: the generic path
+            const bool aligned = k == 0 && !ctx->knobs.force_generic && (uintptr_t)src % 16 == 0 && (stride % 16 == 0 || cnt == 1);
+            const uint32_t threads = top ? WAVE : WG_THREADS, waves_wg = threads / WAVE;
+            uint64_t waves = (nb + FD1_BLOCKS_PER_WAVE - 1) / FD1_BLOCKS_PER_WAVE;
+            if (waves > (1u << 20)) waves = 1u << 20;             // (a wave walks its blocks: any count is covered)
+            const dim3 grid((uint32_t)((waves + waves_wg - 1) / waves_wg), cnt), block(threads);
+            if (aligned)
+                hipLaunchKernelGGL(k_frame_digest<true>, grid, block, 0, ctx->stream, src, stride, len, nb, (uint32_t)top, frame_bytes, dst, dst_stride);
+            else
+                hipLaunchKernelGGL(k_frame_digest<false>, grid, block, 0, ctx->stream, src, stride, len, nb, (uint32_t)top, frame_bytes, dst, dst_stride);
+            src = (const uint8_t *)lvl; stride = nb * 8; len = nb * 8;
+            lvl += (uint64_t)cnt * nb;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+uint64_t rbf_frame_digest_host(const void *bytes, uint64_t nbytes)
+{
+    try { return fd1_host(bytes, (size_t)nbytes); }               // (the levels live in a std::vector: nothing may throw across the C ABI)
+    catch (...) { (void)fail(RBF_ENOMEM, "no host memory for the digest levels of %llu bytes", (unsigned long long)nbytes); return 0; }
 }
 
 }  // extern "C"

@@ -343,14 +343,16 @@ def gather_values(ctx, frame, mask_packed):
     return vals
 
 
-def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild):
+def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt=None):
     """The chunked device-side rebuild of a run of inter-frames after `base` that both record types share (apply_chain below, SampleCoder.
     apply_chain).  The run is rebuilt in chunks of at most `chunk_frames` frames and `chunk_bytes` bytes (1080p YUV444: 41 frames; an 8K
     16-bit frame: one at a time -- device block and host block stay bounded whatever the frame size): one upload of the chunk's predecessor
     into slot 0 of a block of frames `fb`, one of its masks as padded rows `mb`, then rebuild(c0, cnt, fb, mb) has the device write frames
     c0 .. c0+cnt-1 of the run into slots 1 .. cnt, no host round trip in between; the chunk's frames come back in ONE download.
-    alloc(name, nbytes): the device blocks.  Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them
-    alive keeps its whole chunk alive."""
+    alloc(name, nbytes): the device blocks.  on_rebuilt(ptr, frame_bytes, count), optional: called after rebuild(...) and before the chunk's
+    download with the device address of the chunk's `count` rebuilt frames, frame_bytes apart -- where the frame digests of a container
+    with a trailer are taken (integrity.py), from bytes the scatter has just written.  Returns the list of frames.  They are VIEWS of the
+    downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
     H, W, _, _ = nat.frame_geometry(base)
     n = H * W
     stride = nat.packed_stride(n)
@@ -368,16 +370,18 @@ def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild)
         fb.upload(prev, 0)
         mb.upload(nat.mask_rows(masks_packed[c0:c0 + cnt], n))
         rebuild(c0, cnt, fb, mb)
+        if on_rebuilt is not None:
+            on_rebuilt(fb.ptr + fbytes, fbytes, cnt)
         block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
         out += [block[j] for j in range(cnt)]
         prev = block[cnt - 1]
     return out
 
 
-def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20):
+def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None):
     """A8 for a run of inter-frames: frame t = frame t-1 with `values_list[t]` written at mask t's '1' pixels
     (improved_video_compressor.py:849-909), rebuilt ON THE DEVICE in chunks (rebuild_chain): one upload of the chunk's values, then per
-    frame a device-to-device copy of its predecessor and one scatter.
+    frame a device-to-device copy of its predecessor and one scatter.  on_rebuilt: rebuild_chain's hook.
     Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
     base = np.ascontiguousarray(base)
     H, W, C, sb = nat.frame_geometry(base)
@@ -410,7 +414,7 @@ def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_byt
             dst = fb.ptr + (j + 1) * fbytes
             nat.check(L.rbf_memcpy_d2d(ctx.handle, dst, fb.ptr + j * fbytes, fbytes))
             nat.check(L.rbf_scatter_values(ctx.handle, dst, W, H, W * C * sb, C * sb, sb, C, mb.ptr + j * stride, vb.ptr + offs[j]))
-    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild)
+    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt)
     for b in bufs:
         b.free()
     return out

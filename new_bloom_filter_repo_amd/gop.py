@@ -324,6 +324,19 @@ class GopCoder:
         return codec.encode_inter(self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W, self.H,
                                   self.C, self.sb, self.masks.ptr, self.mask_stride, ones)
 
+    def frame_digests(self):
+        """FD1 of the F resident frames of the GOP encode() last coded (integrity.py): ONE rbf_frame_digest_batch over the block -- bytes the
+        hold and the mask stage have just read -- and one download of 8 F bytes; uint64[F].  Call it after encode(): with max_error > 0 the
+        block then holds the HELD frames, which are what the records code and a decoder rebuilds.  (A run's first frame is never written
+        by the hold, rbf_kernels_hold.h: its digest is its original's.)"""
+        if self.frames is None:
+            raise ValueError("frame_digests needs the interleaved frames (keep_interleaved=True)")
+        from .integrity import digests_device
+        if getattr(self, "_digests", None) is None:
+            self._digests = self._alloc(8 * self.F)
+        return digests_device(self.ctx, self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F,
+                              self.frame_bytes, out=self._digests)
+
     def results_packed(self):
         """What results() returns, through ONE exact-size download: the rows are compacted into a record on the device (rbf_pack_records:
         header + the used bytes of every filter and witness, ~150 KB per 1080p frame instead of ~600 KB of padded rows), the record's

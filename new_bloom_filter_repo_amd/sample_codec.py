@@ -158,20 +158,23 @@ class SampleCoder:
         mb = self._buf("pair_mask", stride).upload(nat.mask_rows([mask_packed], H * W))
         return self.encode_inter(fb.ptr, a.nbytes, 2, W, H, C, sb, mb.ptr, stride, [ones])[0]
 
-    def decode_frame(self, stream, height, width, channels, itemsize):
-        """A type-3 stream back to its frame: (H, W) for channels == 0, else (H, W, channels) (rbf_rice_decode_intra)."""
+    def decode_frame(self, stream, height, width, channels, itemsize, on_decoded=None):
+        """A type-3 stream back to its frame: (H, W) for channels == 0, else (H, W, channels) (rbf_rice_decode_intra).
+        on_decoded(ptr, frame_bytes, 1), optional: called with the frame's device address before its download (engine.rebuild_chain's hook)."""
         C = max(1, channels)
         nbytes = height * width * C * itemsize
         fb = self._buf("frame", nbytes)
         src = np.frombuffer(stream, dtype=np.uint8)
         nat.check(nat.lib().rbf_rice_decode_intra(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, fb.ptr))
+        if on_decoded is not None:
+            on_decoded(fb.ptr, nbytes, 1)
         out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
         return out.reshape((height, width) if channels == 0 else (height, width, C))
 
-    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20):
+    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None):
         """engine.apply_chain for type-4 records: frame t = frame t-1 plus the residuals of stream t at mask t's '1' pixels, rebuilt on the
-        device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  Returns the frames
-        as views of the downloaded chunk blocks."""
+        device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  on_rebuilt:
+        rebuild_chain's hook.  Returns the frames as views of the downloaded chunk blocks."""
         base = np.ascontiguousarray(base)
         H, W, C, sb = nat.frame_geometry(base)
         stride = nat.packed_stride(H * W)
@@ -181,4 +184,4 @@ class SampleCoder:
             blob = np.frombuffer(b"".join(part), dtype=np.uint8)
             sizes = (ctypes.c_uint64 * cnt)(*[len(s) for s in part])
             nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, sb, mb.ptr, stride, fb.ptr))
-        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild)
+        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt)

@@ -3,6 +3,7 @@ verify_lossless  -- FixedVideoCompressor.verify_lossless (fixed_video_compressor
 verify_bit_exact -- verify_true_lossless.verify_bit_exact (verify_true_lossless.py:338-492),
                     without the OpenCV diagnostic image dumps.
 verify_max_error -- the near-lossless mode's guarantee (ImprovedVideoCompressor(max_error=...)); the reference has no counterpart.
+verify_container -- a container against its own frame digests (ImprovedVideoCompressor(frame_digests=True)): needs no originals.
 Unlike the reference (which unwraps with `hasattr(x, 'data')` and then crashes on unequal plain
 ndarrays, whose `.data` is a memoryview) both accept plain ndarrays and YUVFrame wrappers."""
 import numpy as np
@@ -91,3 +92,34 @@ def verify_max_error(original_frames, decoded_frames, max_error, keyframe_interv
     if keyframe_interval:
         out["keyframes_exact"] = keys_exact
     return out
+
+
+def verify_container(path_or_bytes, **compressor_kwargs):
+    """Decode a container (a path, or its bytes) and check every frame against the digests it stores (integrity.py), without raising on a
+    frame mismatch: {"frames": frames decoded, "checked": frames compared with a stored digest, "bad": [indices of the frames whose digest
+    does not match], "trailer": "ok" | "absent" (nothing to check against) | "damaged" (the trailer itself is not usable: the frames are
+    decoded, none is checked)}.  compressor_kwargs go to the ImprovedVideoCompressor that decodes (chain_chunk_frames: its attribute of
+    that name).  What the records themselves make undecodable still raises."""
+    from . import container
+    from .video_compressor import ImprovedVideoCompressor
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        blob = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            blob = f.read()
+    records = container.parse(blob)
+    try:
+        _, stored = container.split_trailer(records)
+        trailer = "absent" if stored is None else "ok"
+    except ValueError:
+        trailer = "damaged"
+        records = [r for r in records if r[0] != container.DIGESTS]
+    chunk = compressor_kwargs.pop("chain_chunk_frames", None)
+    comp = ImprovedVideoCompressor(**compressor_kwargs)
+    if chunk is not None:
+        comp.chain_chunk_frames = int(chunk)
+    try:
+        frames = comp.decompress_video(compressed_frames=records, on_mismatch="collect")
+        return {"frames": len(frames), "checked": comp.last_integrity["checked"], "bad": list(comp.last_bad_frames), "trailer": trailer}
+    finally:
+        comp.close()

@@ -9,7 +9,8 @@ threshold 0 must cover every changed pixel); otherwise that frame falls back to 
 mask of every pixel in which any sample changed instead, which covers every change by construction.
 
 Container and record types: container.py.  sample_codec="rice" writes types 3 and 4 instead of 1 and 2: the same two roles with the GPU
-sample codec (sample_codec.py) in place of zlib-9.
+sample codec (sample_codec.py) in place of zlib-9.  frame_digests=True appends a type-5 record: one digest per frame (integrity.py), which
+decompress_video checks against what it rebuilt.
 """
 import contextlib
 import os
@@ -25,8 +26,9 @@ import numpy as np
 from . import container
 from . import params as P
 from ._native import frame_geometry
-from .container import INTER, INTER_RICE, KEY, KEY_RICE, KEYS, blocks_off_keyframes, is_keyframe, plan_range
+from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, blocks_off_keyframes, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
+from .integrity import IntegrityError, build_trailer, digests_device, frame_digest_host
 from .sample_codec import key_format, key_record, parse_key_record, stream_info
 
 _POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)   # numpy 1.x has no bitwise_count
@@ -64,6 +66,14 @@ class _Lane:
         self.coders = {}
         self.engine = None
         self.samples = None
+        self.scratch = None
+
+    def digests(self, ptr, stride, nframes, frame_bytes):
+        """integrity.digests_device on this lane, into a block the lane keeps (no allocation per chunk of a run)."""
+        if self.scratch is None:
+            from ._native import BufferCache
+            self.scratch = BufferCache(self.ctx)
+        return digests_device(self.ctx, ptr, stride, nframes, frame_bytes, out=self.scratch.get("digests", 8 * nframes))
 
     def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0):
         from .gop import GopCoder
@@ -99,6 +109,9 @@ class _Lane:
         if self.samples is not None:
             self.samples.close()
             self.samples = None
+        if self.scratch is not None:
+            self.scratch.close()
+            self.scratch = None
 
     def close(self):
         self.release()
@@ -133,6 +146,11 @@ class _LanePool:
             return list(gpu_pool.map(lambda job: fn(job, self.take), jobs))
 
 
+class _BlockRecords(list):
+    """What _encode_block returns: the per-pair list, with the block's frame digests (uint64 per frame of the block, or None)."""
+    digests = None
+
+
 def _union_seconds(intervals):
     """Total length of the union of (t0, t1) intervals."""
     total, end = 0.0, None
@@ -157,8 +175,9 @@ class ImprovedVideoCompressor:
     def __init__(self, noise_tolerance=10.0, keyframe_interval=30, min_diff_threshold=3.0,
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
-                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0):
-        """Reference signature (improved_video_compressor.py:318-327) plus eight keyword-only extras:
+                 gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
+                 frame_digests=False, verify_digests=True):
+        """Reference signature (improved_video_compressor.py:318-327) plus ten keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -183,10 +202,22 @@ class ImprovedVideoCompressor:
         pixels.  Needs mask_channels="all", inter-frames, gop_batching=True, and blocks that start at keyframes (encode_range raises
         otherwise: block_frames a multiple of keyframe_interval, a range that starts on a keyframe).  A block the GPU cannot batch is
         coded exactly, which satisfies the bound.  The reference's noise_tolerance / min_diff_threshold / max_diff_threshold stay
-        accepted and unused."""
+        accepted and unused.
+        frame_digests: False (default) -- the container is today's, byte for byte.  True -- compress_video appends a type-5 record with one
+        FD1 digest per frame (integrity.py; the container is then always 'BFV2'): of the frame the decoder must rebuild, so with
+        max_error > 0 of the HELD frame.  Frames coded from a resident block are digested there, on the GPU, in one launch sequence per
+        block; frames that reach the container from the caller's arrays (keyframes, the frame-by-frame route) by the host twin.
+        verify_digests: True (default) -- decompress_video checks a container's digests, inter-frames on the GPU from the block they are
+        rebuilt in, and raises IntegrityError at the first frame (in stream order) that does not match; False -- the trailer is parsed and
+        ignored.  A container without one decodes as ever.  last_integrity says how many frames were checked, and where."""
         if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
             raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
         self.max_error = int(max_error)
+        self.frame_digests, self.verify_digests = bool(frame_digests), bool(verify_digests)
+        self.last_digests = None                 # frame_digests=True: the digests of the last encode_range's frames, aligned with its records
+        self.last_integrity = None               # {"frames", "checked", "device", "host"} of the last decompress_video
+        self.last_bad_frames = None              # ... and the frames whose digest did not match (decompress_video(on_mismatch="collect"))
+        self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
         if self.max_error:
             if mask_channels != "all":
                 raise ValueError("max_error > 0 holds every sample of a pixel: it needs mask_channels='all'")
@@ -316,7 +347,8 @@ class ImprovedVideoCompressor:
         shard's halo frame), every other frame is coded against its predecessor -- except the frames named in `run_starts` (indices
         into seg), which are keyframes of the stream: they start a new run and the pair in front of them is not coded.  One upload,
         ONE rbf_encode_runs launch sequence for all the runs, ONE exact-size download of the packed record (rbf_pack_records), one
-        batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.
+        batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.  With
+        frame_digests the block's frames are digested where they lie, after the hold (GopCoder.frame_digests): the list's `digests`.
         lane: the context and coders to use (default: lane 0); busy: list that receives the (start, end) time of this block's GPU work.
         Returns a list of futures / None per pair (None = needs a keyframe, or is one), or None when the block cannot be batched
         (mixed shapes or dtypes)."""
@@ -329,7 +361,7 @@ class ImprovedVideoCompressor:
             return None
         H, W, C, sb = frame_geometry(a)
         if C > 4:                                # rbf_gather_values_batch carries at most 4 samples per pixel
-            return [None] * (len(seg) - 1)
+            return _BlockRecords([None] * (len(seg) - 1))
         if lane is None:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
@@ -345,6 +377,7 @@ class ImprovedVideoCompressor:
             ctx.sync()
         t3 = time.perf_counter()
         res = coder.results_packed()
+        block_digests = coder.frame_digests() if self.frame_digests else None
         t4 = time.perf_counter()
         rice = self.sample_codec == "rice"
         if mc == 1:
@@ -358,7 +391,8 @@ class ImprovedVideoCompressor:
         if busy is not None:
             busy.append((t1, t5))
         n = H * W
-        out = []
+        out = _BlockRecords()
+        out.digests = block_digests
         broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
         for f, r in enumerate(res):
             if r.get("skipped"):                 # the pair in front of a keyframe
@@ -396,7 +430,8 @@ class ImprovedVideoCompressor:
         several GOPs per block, ONE launch sequence on the GPU per block, cut at the keyframes (plan_range).  The blocks alternate over
         `gpu_lanes` contexts, each block on its own host thread; the host's zlib-9 (keyframes: four jobs each; changed values:
         one job per frame) runs on `num_threads` threads under all of it.  release: return the lanes' device memory as soon as the last
-        block has left the GPU (False: keep the coders for the next call of the same geometry)."""
+        block has left the GPU (False: keep the coders for the next call of the same geometry).
+        frame_digests=True: self.last_digests holds one digest per returned record (of the frame a decoder rebuilds from it), else None."""
         records = {}
         I = self.keyframe_interval
         inter_type = INTER_RICE if self.sample_codec == "rice" else INTER
@@ -411,8 +446,20 @@ class ImprovedVideoCompressor:
                 raise ValueError("max_error=%d: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
                                  "another block's coder; make block_frames (%d) a multiple of keyframe_interval (%d) and start the range "
                                  "on a keyframe" % (self.max_error, off[0][0], self.block_frames, I))
+        want = self.frame_digests
+        digests = {}                             # frame -> its digest, or the future of the host twin's
+        in_block = {u for lo, end, _ in blocks for u in range(lo, end)} if self.gop_batching else set()
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
+
+            def digest_of(u, block_digests=None, j=0):
+                """Frame u's digest: entry j of its block's (taken on the GPU from the resident frames), else the host twin's of the caller's array."""
+                if not want or u in digests or not start <= u < stop:
+                    return
+                if block_digests is not None:
+                    digests[u] = int(block_digests[j])
+                else:
+                    digests[u] = pool.submit(frame_digest_host, frame_data(frames[u - first_index]))
 
             def key(t):
                 if t in pending or t in gpu_keys:
@@ -430,6 +477,8 @@ class ImprovedVideoCompressor:
             # frame, plus its three planes) then runs under the GPU's blocks instead of behind the last one
             for t in fixed_keys:
                 key(t)
+                if t not in in_block:            # (a keyframe inside a block is digested there, with the block's other frames)
+                    digest_of(t)
             results = self._on_lanes(blocks, run_block) if self.gop_batching and blocks else [None] * len(blocks)
             tm["gpu_phase"] = time.perf_counter() - t_all                    # until the last block's values were on the host
             if release:                                                      # the lanes' blocks of frames, masks, filters and witnesses go back while the
@@ -438,20 +487,31 @@ class ImprovedVideoCompressor:
                 tm["release"] = time.perf_counter() - t_rel
             for (lo, end, starts), inter in zip(blocks, results):
                 seg = frames[lo - first_index:end - first_index]             # predecessor + the frames lo+1..end-1
+                # The block's digests describe its frames AFTER the hold.  The hold never writes a run's first frame (rbf_kernels_hold.h:
+                # "frame first[y] is never written"), so the block's first frame and the keyframes inside it -- the run starts handed to
+                # the coder -- still are the caller's originals, which is what their keyframe records code: their digests are taken
+                # from the block too.  Not so a frame that falls back to a keyframe with max_error > 0: its record codes the original,
+                # the block holds the held frame -- the host twin digests the original.
+                bd = getattr(inter, "digests", None)
+                digest_of(lo, bd, 0)
                 for j in range(1, len(seg)):
                     u = lo + j
                     if is_keyframe(u, first_index, I):
                         key(u)
+                        digest_of(u, bd, j)
                         continue
                     if inter is None:                                        # not batchable (or gop_batching=False): frame by frame
+                        digest_of(u)
                         rec = self._encode_inter(seg[j - 1], seg[j])
                         if rec is not None:
                             records[u] = (inter_type, rec)
                             continue
                     elif inter[j - 1] is not None:
                         pending[u] = (inter_type, inter[j - 1])
+                        digest_of(u, bd, j)
                         continue
                     key(u)
+                    digest_of(u, None if self.max_error else bd, j)
             if gpu_keys:
                 t_key = time.perf_counter()
                 for u, rec in self._encode_keys_rice(frames, first_index, sorted(gpu_keys), busy).items():
@@ -463,6 +523,7 @@ class ImprovedVideoCompressor:
             for u, (ty, fut) in pending.items():
                 records[u] = (ty, fut() if ty == KEY else fut.result())
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
+            self.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (digests[u] for u in range(start, stop))] if want else None
         _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
         return [records[u] for u in range(start, stop)]
@@ -488,13 +549,15 @@ class ImprovedVideoCompressor:
         outs = self._on_lanes(batches, run)
         return {t: rec for (_, ts_b), recs in zip(batches, outs) for t, rec in zip(ts_b, recs)}
 
-    def _decode_key_rice(self, rec, lane=None, busy=None):
-        """A type-3 keyframe decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so."""
+    def _decode_key_rice(self, rec, lane=None, busy=None, digest_out=None):
+        """A type-3 keyframe decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so.  digest_out: a list that
+        receives the frame's digest, taken on the device where the frame was decoded, before its download."""
         d = parse_key_record(rec)
         if lane is None:
             lane = self._get_lanes(1)[0]
         t0 = time.perf_counter()
-        frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"])
+        hook = None if digest_out is None else (lambda ptr, nbytes, cnt: digest_out.extend(int(x) for x in lane.digests(ptr, nbytes, cnt, nbytes)))
+        frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], on_decoded=hook)
         if busy is not None:
             busy.append((t0, time.perf_counter()))
         return YUVFrame(frame) if d["yuv"] else frame
@@ -518,6 +581,8 @@ class ImprovedVideoCompressor:
             records = self.encode_range(frames, 0, 0, len(frames), inter_frames=use_inter)
         finally:
             self._release_lanes()                # (an exception in front of encode_range's own release)
+        if self.frame_digests:                   # the trailer: one digest per frame record, behind them all
+            records = records + [(DIGESTS, build_trailer(self.last_digests))]
         self.last_compressed_frames = records
         keyframes = sum(1 for ty, _ in records if ty in KEYS)
         if output_path:
@@ -550,7 +615,14 @@ class ImprovedVideoCompressor:
     _parse_container = staticmethod(container.parse)
 
     # ------------------------------------------------------------------ decode
-    def decompress_video(self, input_path=None, output_path=None, compressed_frames=None, metadata=None):
+    def decompress_video(self, input_path=None, output_path=None, compressed_frames=None, metadata=None, on_mismatch="raise"):
+        """The frames of a container (input_path) or of its records (compressed_frames).  A container with a digest trailer is checked
+        unless verify_digests=False: every inter-frame on the GPU, from the chain block it is rebuilt in; a type-3 keyframe on the GPU
+        where it is decoded; a type-1 keyframe by the host twin on the thread that inflated it.  The first frame, in stream order, whose
+        digest is not the stored one raises IntegrityError (on_mismatch="collect": no exception, self.last_bad_frames lists them all --
+        verify.verify_container).  self.last_integrity = {"frames", "checked", "device", "host"}."""
+        if on_mismatch not in ("raise", "collect"):
+            raise ValueError("on_mismatch must be 'raise' or 'collect', got %r" % (on_mismatch,))
         start = time.time()
         t_all = time.perf_counter()
         records = None
@@ -561,6 +633,12 @@ class ImprovedVideoCompressor:
             records = [r if isinstance(r, tuple) else (KEY, r) for r in compressed_frames]
         if not records:
             raise ValueError("No compressed frames provided")
+        records, stored = container.split_trailer(records)                   # (a damaged trailer is a plain ValueError here: not a damaged frame)
+        if not records:
+            raise ValueError("No compressed frames provided")
+        expected = stored if self.verify_digests else None
+        check = expected is not None
+        got = {}                                                             # record index -> (digest of the rebuilt frame, "device" | "host")
         types = [ty for ty, _ in records]
         container.check_types(types)
         self.last_timing = tm = {}
@@ -568,20 +646,43 @@ class ImprovedVideoCompressor:
         # the keyframes are independent of everything else: inflate them on the host threads while the inter-frame runs go through the GPU
         # (type-3 keyframes are decoded on the lanes: by the run that hangs off them, or by a job of their own)
         key_pool = ThreadPoolExecutor(self.num_threads)
-        keys = {j: key_pool.submit(self.compressor.decompress_frame, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
+        def key_job(rec):
+            frame = self.compressor.decompress_frame(rec)
+            return frame, frame_digest_host(frame_data(frame)) if check else None
+        keys = {j: key_pool.submit(key_job, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
         gkeys = {}
         runs = container.inter_runs(types)                                   # (index of the keyframe in front, first record, end)
         decoded = {}
 
+        class dev_digest(list):
+            """A list that files what it receives as the device digests of the records first, first + 1, ..."""
+
+            def __init__(self, first, count):
+                super().__init__()
+                self.first = first
+
+            def extend(self, values):
+                for v in values:
+                    got[self.first + len(self)] = (int(v), "device")
+                    self.append(v)
+        if not check:
+            dev_digest = lambda first, count: None                          # noqa: E731
+
+        def host_digests(first, decoded_frames):
+            if check:
+                for i, f in enumerate(decoded_frames):
+                    got[first + i] = (frame_digest_host(frame_data(f)), "host")
+
         def run_job(job, take):
             k, lo, hi = job
-            base = keys[k].result() if types[k] == KEY else None             # (waits for the host's inflate without holding a lane)
+            base = keys[k].result()[0] if types[k] == KEY else None          # (waits for the host's inflate without holding a lane)
             with take() as lane:
                 if base is None:
-                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy)
+                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=dev_digest(k, 1))
                 if lo is None:
                     return None
-                return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi])
+                return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi],
+                                        digests_out=dev_digest(lo, hi - lo))
         try:
             bases = {k for k, _, _ in runs}
             jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty == KEY_RICE and j not in bases]     # lone type-3 keyframes: no run
@@ -597,18 +698,31 @@ class ImprovedVideoCompressor:
             while i < len(records):
                 if i not in ends:                                            # a keyframe
                     if types[i] == KEY:
-                        frames.append(keys[i].result())
+                        frame, digest = keys[i].result()
+                        frames.append(frame)
+                        if check:
+                            got[i] = (digest, "host")
                     else:
-                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1]))
+                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=dev_digest(i, 1)))
                     i += 1
                     continue
-                frames += decoded[i] if i in decoded else self._decode_frame_by_frame(frames[-1], records[i:ends[i]])
+                if i in decoded:
+                    frames += decoded[i]
+                else:
+                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]])
+                    host_digests(i, frames[i:ends[i]])
                 i = ends[i]
         finally:
             key_pool.shutdown(wait=True)
             self._release_lanes()
         _close_timing(tm, t_all, busy)
         tm["runs"], tm["lanes"] = len(runs), min(self.gpu_lanes, max(1, len(runs)))
+        self.last_integrity = {"frames": len(frames), "checked": len(got), "device": sum(1 for _, where in got.values() if where == "device"),
+                               "host": sum(1 for _, where in got.values() if where == "host")}
+        self.last_bad_frames = [i for i in sorted(got) if got[i][0] != expected[i]]
+        if self.last_bad_frames and on_mismatch == "raise":
+            i = self.last_bad_frames[0]
+            raise IntegrityError(i, expected[i], got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEYS))
         if output_path:
             self.save_frames_as_video(frames, output_path)
         if self.verbose:
@@ -662,11 +776,13 @@ class ImprovedVideoCompressor:
                     raise ValueError("changed_values does not match the mask")
                 masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None):
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None):
         """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
         ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
         rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
-        (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2)."""
+        (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2);
+        digests_out: a list that receives the digest of every rebuilt frame, in order -- taken on the device from the chain block, after
+        the rebuild of a chunk and before its download (engine.rebuild_chain's hook)."""
         from .engine import apply_chain
         if lane is None:
             lane = self._get_lanes(1)[0]
@@ -697,14 +813,16 @@ class ImprovedVideoCompressor:
         self._fit_values(parsed, masks, vals, n, ch)
         t4 = time.perf_counter()
         out, prev, i = [], base_arr, 0
+        hook = None if digests_out is None else (lambda ptr, fbytes, cnt: digests_out.extend(int(x) for x in lane.digests(ptr, fbytes, cnt, fbytes)))
+        chunk = self.chain_chunk_frames
         while i < len(parsed):                   # stretches of one record type: values written (type 2) or residuals added (type 4)
             j = i
             while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
                 j += 1
             if parsed[i]["rice"]:
-                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j])
+                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook)
             else:
-                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j])
+                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook)
             out += part
             prev, i = part[-1], j
         t5 = time.perf_counter()
