@@ -209,6 +209,30 @@ int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride
                            uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                            uint32_t max_error, const uint8_t *run_starts);
 
+/* ---- A1, near-lossless: look-ahead temporal hold -------------------------------------------------- */
+/* rbf_temporal_hold_runs with another decision rule; the same arguments, layout, runs, checks, error codes and no-op cases.  The hold
+ * above keeps a pixel while its samples stay within e = max_error of the segment's FIRST value, so sensor noise of +-a needs e >= 2a.
+ * The bound only asks that a segment's samples fit one window of width 2e, so this rule lets a segment run for as long as the windows
+ * [x_t - e, x_t + e] of its frames still intersect (greedy interval stabbing: the fewest updates for a fixed first value), and noise of
+ * +-a needs e >= a.  Per pixel and run, M = 2^(8*sample_bytes) - 1, true integer differences (no wrap):
+ *     y_0 = x_0; a run's first frame is never written.
+ *     Anchored segment: while |x_t[c] - x_0[c]| <= e for EVERY sample c, y_t = x_0 (the keyframe is coded exactly).
+ *     At the first frame t that breaks this a free segment opens with lo[c] = max(0, x_t[c] - e), hi[c] = min(M, x_t[c] + e).
+ *     A following frame u gives lo' = max(lo, max(0, x_u - e)), hi' = min(hi, min(M, x_u + e)); if lo'[c] > hi'[c] for ANY sample the
+ *     segment ends at u - 1 and a new free segment opens at u, else lo, hi = lo', hi'.  The end of the run ends the last segment.
+ *     A free segment's value is v[c] = clamp(prev[c], lo[c], hi[c]) with prev the previous segment's value (x_0 after the anchored one);
+ *     every frame of the segment becomes v, the whole pixel.
+ * So |y_t - x_t| <= max_error everywhere, y_t differs from y_{t-1} exactly at the frames where a segment opens (the exact all-channel
+ * mask of the result is the set of segment starts), and the samples of a breaking pixel that can keep their value do.  No pixel is
+ * updated more often than by rbf_temporal_hold_runs.  NOT idempotent: applied to its own output it can merge segments and double the
+ * error -- call it once per uploaded block.  Deterministic (no atomics).  Asynchronous on the context's stream.  Two sweeps over the
+ * block and a scratch bitmap of nframes * ceil(width*height/8) bytes that the context keeps.  Frames whose base and stride are
+ * multiples of 8 go through 8-byte accesses, any other sample-aligned layout and the last (width*height) % 8 pixels of a frame through
+ * a per-pixel kernel.  Timed under RBF_K_HOLD. */
+int rbf_temporal_lookahead_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                                uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                                uint32_t max_error, const uint8_t *run_starts);
+
 /* ---- A1, BGR input  (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY), :794-795) --------------------- */
 /* gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15 per pixel -- OpenCV 4.x's integer path for 8- and
  * 16-bit samples; samples 0,1,2 of a pixel are B,G,R (further channels are ignored).  gray_dev receives

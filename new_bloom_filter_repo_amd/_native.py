@@ -75,6 +75,7 @@ _PROTOS = {
     "rbf_residual_mask_batch": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp]),
     "rbf_residual_mask_batch_ex": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp, _u32]),
     "rbf_temporal_hold_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "rbf_temporal_lookahead_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_record_max_bytes": (_u64, [_u32, _u64]),
     "rbf_pack_records": (_int, [_vp, _u32, _u64, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double),
                                 _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64]),

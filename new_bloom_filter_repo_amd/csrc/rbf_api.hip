@@ -9,6 +9,7 @@
 #include "rbf_kernels_noise.h"
 #include "rbf_kernels_mask.h"
 #include "rbf_kernels_hold.h"
+#include "rbf_kernels_lookahead.h"
 #include "rbf_kernels_barrett.h"
 #include "rbf_kernels_insert_f64.h"
 #include "rbf_kernels_reduce.h"
@@ -985,6 +986,70 @@ int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride
         count = 0;
     };
     // the runs: frame 0 and every marked frame start one; a run of one frame has nothing to hold
+    for (uint32_t a = 0; a < nframes;) {
+        uint32_t b = a + 1;
+        while (b < nframes && !(run_starts && run_starts[b])) ++b;
+        if (b - a >= 2) {
+            runs.first[count] = a; runs.len[count] = b - a;
+            if (++count == HOLD_MAX_RUNS) flush();
+        }
+        a = b;
+    }
+    flush();
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+// ---- A1, near-lossless: the look-ahead hold (rbf_kernels_lookahead.h) -- the same checks, runs and no-op cases as the hold above
+int rbf_temporal_lookahead_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                                uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                                uint32_t max_error, const uint8_t *run_starts)
+{
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    if (int r = check_layout(l, nframes, rules)) return r;
+    if (max_error >> (8 * sample_bytes)) return fail(RBF_ERANGE, "max_error %u does not fit a %u-bit sample", max_error, 8 * sample_bytes);
+    if (max_error == 0 || nframes < 2) return RBF_OK;             // y = x
+    if (!frames_dev) return fail(RBF_EINVAL, "null device pointer");
+    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    // lane tiles of 8 pixels through 8-byte accesses where the layout allows them, the per-pixel kernel for everything else
+    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 8 == 0 && frame_stride_bytes % 8 == 0;
+    const uint64_t lanes = vec ? n / LA_LANE_PIXELS : 0, first_px = lanes * LA_LANE_PIXELS;
+    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
+    if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    const uint64_t bits_stride = (n + 7) / 8;                     // the segment-start bits: a row per frame, a byte per lane tile
+    if (lanes)
+        if (int r = ctx->hold_bits.reserve((size_t)nframes * bits_stride)) return r;
+    uint8_t *const frames = (uint8_t *)frames_dev, *const bits = ctx->hold_bits.p;
+    HoldRuns runs{};
+    uint32_t count = 0;
+    auto flush = [&]() {
+        if (!count) return;
+        LaunchTimer t(ctx, RBF_K_HOLD);
+        if (lanes) {
+            const dim3 grid((uint32_t)bx_lanes, count), block(WG_THREADS);
+#define RBF_LA(S, C)                                                                                                                             \
+    do {                                                                                                                                         \
+        hipLaunchKernelGGL((k_temporal_lookahead<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, bits, bits_stride, runs); \
+        hipLaunchKernelGGL((k_lookahead_fill<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bits, bits_stride, runs);   \
+    } while (0)
+            if (sample_bytes == 1) { if (channels == 1) RBF_LA(uint8_t, 1); else if (channels == 2) RBF_LA(uint8_t, 2); else if (channels == 3) RBF_LA(uint8_t, 3); else RBF_LA(uint8_t, 4); }
+            else { if (channels == 1) RBF_LA(uint16_t, 1); else if (channels == 2) RBF_LA(uint16_t, 2); else if (channels == 3) RBF_LA(uint16_t, 3); else RBF_LA(uint16_t, 4); }
+#undef RBF_LA
+        }
+        if (first_px < n)
+            by_sample_width(sample_bytes, [&](auto s) {
+                hipLaunchKernelGGL(k_temporal_lookahead_px<decltype(s)>, dim3((uint32_t)bx_px, count), dim3(WG_THREADS), 0, ctx->stream, frames,
+                                   frame_stride_bytes, first_px, n, channels, max_error, runs);
+            });
+        count = 0;
+    };
     for (uint32_t a = 0; a < nframes;) {
         uint32_t b = a + 1;
         while (b < nframes && !(run_starts && run_starts[b])) ++b;

@@ -62,7 +62,7 @@ class GopCoder:
     def __init__(self, ctx, width, height, nframes, channels=3, sample_bytes=1, seeds=P.SEEDS_VIDEO,
                  allocator=None, threshold=0.0, out_allocator=None, frames_block=None, adaptive=None,
                  planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None, mask_channels=1,
-                 max_error=0):
+                 max_error=0, hold_mode="first"):
         """allocator: device memory source (default: library-owned); out_allocator: separate source for
         the output record (filters, witnesses, stats); frames_block: share another coder's frame buffer.
         threshold=None with adaptive=(noise_tolerance, min_thr, max_thr): per-frame noise-adaptive
@@ -83,6 +83,12 @@ class GopCoder:
         rice_streams() read the held frames (that is what makes the records consistent), and so does every other coder that shares the
         block through frames_block.  The hold is idempotent, so encoding a resident GOP again gives the same rows.  Needs a mask that
         sees every sample (mask_channels == channels, or channels == 1); not with planar_luma, adaptive or a non-zero threshold.
+        hold_mode: "first" (default) = that hold: a pixel is kept while its samples stay within max_error of the segment's first value.
+        "lookahead" (needs max_error > 0) = the look-ahead hold (rbf_temporal_lookahead_runs): a segment lasts while the windows
+        [x - max_error, x + max_error] of its frames intersect, so sensor noise of +-a is held at max_error = a instead of 2a; the same
+        bound, the same exact run firsts, never more updates per pixel.  It is NOT idempotent, so the coder runs it ONCE PER load_frames():
+        a second encode() of the same resident GOP skips the stage -- the block already is its held sequence -- and returns the same rows.
+        (A block shared through frames_block, or filled behind the coder's back, is the caller's to keep track of: mark_loaded().)
         """
         from .engine import threshold_floor
         self.mask_channels = int(mask_channels)
@@ -110,6 +116,12 @@ class GopCoder:
                 raise ValueError("max_error > 0 codes the held frames exactly: no adaptive thresholds")
             if not np.ndim(threshold) == 0 or float(threshold) != 0.0:
                 raise ValueError("max_error > 0 codes the held frames exactly: threshold must be 0, got %r" % (threshold,))
+        if hold_mode not in ("first", "lookahead"):
+            raise ValueError("hold_mode must be 'first' or 'lookahead', got %r" % (hold_mode,))
+        if hold_mode == "lookahead" and not self.max_error:
+            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0")
+        self.hold_mode = hold_mode
+        self._held = set()                            # look-ahead: the resident GOPs that already are their held sequence
         self.ctx, self.W, self.H, self.F, self.C, self.sb = ctx, width, height, nframes, channels, sample_bytes
         self.n = width * height
         self.pairs = nframes - 1
@@ -197,6 +209,7 @@ class GopCoder:
         frames = np.ascontiguousarray(frames)
         assert frames.nbytes == self.frame_bytes * self.F, (frames.shape, frames.dtype)
         assert 0 <= gop < self.resident_gops
+        self.mark_loaded(gop)
         if self.frames is not None:
             dst = self.frames.ptr + gop * self.frame_bytes * self.F
             nat.check(nat.lib().rbf_memcpy_h2d(self.ctx.handle, dst, frames.ctypes.data, frames.nbytes))
@@ -205,6 +218,11 @@ class GopCoder:
                                                            self.C * self.sb, self.sb, self.luma.ptr + gop * self.luma_bytes * self.F))
         else:
             self.load_luma(frames.reshape(self.F, self.H, self.W, self.C)[..., 0], gop)
+
+    def mark_loaded(self, gop=0):
+        """Slot `gop` holds new input frames (load_frames() calls this; a caller that fills the block some other way does): the next
+        encode() of it runs the look-ahead hold again."""
+        self._held.discard(gop)
 
     def load_luma(self, planes, gop=0):
         """Upload one GOP of dense (F, H, W) Y planes (planar_luma coders)."""
@@ -255,7 +273,12 @@ class GopCoder:
             src, fstride, pitch, pstride = self.luma.ptr + gop * self.luma_bytes * self.F, self.luma_bytes, self.W * self.sb, self.sb
         else:
             src, fstride, pitch, pstride = self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.W * self.C * self.sb, self.C * self.sb
-        if self.max_error:                            # near-lossless: the block becomes its held sequence, which is then coded exactly
+        if self.max_error and self.hold_mode == "lookahead":
+            if gop not in self._held:                 # not idempotent: once per load_frames(); after that the block IS its held sequence
+                nat.check(nat.lib().rbf_temporal_lookahead_runs(self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb,
+                                                                self.max_error, self.run_starts))
+                self._held.add(gop)
+        elif self.max_error:                          # near-lossless: the block becomes its held sequence, which is then coded exactly
             nat.check(nat.lib().rbf_temporal_hold_runs(self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb, self.max_error,
                                                        self.run_starts))
         nat.check(nat.lib().rbf_encode_runs_begin_ex(

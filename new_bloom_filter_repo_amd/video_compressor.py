@@ -75,16 +75,17 @@ class _Lane:
             self.scratch = BufferCache(self.ctx)
         return digests_device(self.ctx, ptr, stride, nframes, frame_bytes, out=self.scratch.get("digests", 8 * nframes))
 
-    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0):
+    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0, hold_mode="first"):
         from .gop import GopCoder
-        key = (W, H, F, C, sb, mask_channels, max_error)
+        key = (W, H, F, C, sb, mask_channels, max_error, hold_mode)
         c = self.coders.get(key)
         if c is None:
             if len(self.coders) >= 2:            # a stream has at most two block sizes (full blocks and its tail)
                 for old in self.coders.values():
                     old.close()
                 self.coders = {}
-            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels, max_error=max_error)
+            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels, max_error=max_error,
+                                                hold_mode=hold_mode)
         return c
 
     def decode_engine(self):
@@ -176,8 +177,8 @@ class ImprovedVideoCompressor:
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
-                 frame_digests=False, verify_digests=True):
-        """Reference signature (improved_video_compressor.py:318-327) plus ten keyword-only extras:
+                 frame_digests=False, verify_digests=True, hold_mode="first"):
+        """Reference signature (improved_video_compressor.py:318-327) plus eleven keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -203,6 +204,10 @@ class ImprovedVideoCompressor:
         otherwise: block_frames a multiple of keyframe_interval, a range that starts on a keyframe).  A block the GPU cannot batch is
         coded exactly, which satisfies the bound.  The reference's noise_tolerance / min_diff_threshold / max_diff_threshold stay
         accepted and unused.
+        hold_mode: "first" (default) -- the rule above: a pixel is held while it stays within max_error of the value it was last coded
+        with, so sensor noise of +-a needs max_error >= 2a before the masks get sparse.  "lookahead" (needs max_error > 0) -- a pixel's
+        segment lasts while the windows [x - max_error, x + max_error] of its frames still intersect (GopCoder(hold_mode="lookahead"):
+        the look-ahead hold on the GPU), so max_error = a is enough; the same bound, exact keyframes and records, never more updates.
         frame_digests: False (default) -- the container is today's, byte for byte.  True -- compress_video appends a type-5 record with one
         FD1 digest per frame (integrity.py; the container is then always 'BFV2'): of the frame the decoder must rebuild, so with
         max_error > 0 of the HELD frame.  Frames coded from a resident block are digested there, on the GPU, in one launch sequence per
@@ -213,6 +218,11 @@ class ImprovedVideoCompressor:
         if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
             raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
         self.max_error = int(max_error)
+        if hold_mode not in ("first", "lookahead"):
+            raise ValueError("hold_mode must be 'first' or 'lookahead', got %r" % (hold_mode,))
+        if hold_mode == "lookahead" and not self.max_error:
+            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0")
+        self.hold_mode = hold_mode
         self.frame_digests, self.verify_digests = bool(frame_digests), bool(verify_digests)
         self.last_digests = None                 # frame_digests=True: the digests of the last encode_range's frames, aligned with its records
         self.last_integrity = None               # {"frames", "checked", "device", "host"} of the last decompress_video
@@ -366,7 +376,7 @@ class ImprovedVideoCompressor:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
         mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
-        coder = lane.coder(W, H, len(seg), C, sb, mc, self.max_error)
+        coder = lane.coder(W, H, len(seg), C, sb, mc, self.max_error, self.hold_mode)
         coder.set_run_starts(list(run_starts))
         block = _as_block(data)
         t1 = time.perf_counter()
@@ -602,6 +612,7 @@ class ImprovedVideoCompressor:
                    "output_path": output_path, "color_space": input_color_space, "overall_ratio": ratio}
         if self.max_error:
             results["max_error"] = self.max_error
+            results["hold_mode"] = self.hold_mode
         if self.verbose:
             print("\\nCompression Results:")
             print(f"Original Size: {original_size / (1024 * 1024):.2f} MB")
