@@ -508,6 +508,32 @@ int rbf_frame_digest_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_
                            uint64_t frame_bytes, uint64_t *digests_dev);
 uint64_t rbf_frame_digest_host(const void *bytes, uint64_t nbytes);
 
+/* ---- scene cuts: is a frame cheaper as a keyframe than as an inter-frame? -------------------------------------------------------- */
+/* Read-only, on nframes dense interleaved frames (the layout of rbf_temporal_hold_runs: frame f at frames_dev + f*frame_stride_bytes, a
+ * frame is width*height pixels of `channels` (1..4) samples of B = 8*sample_bytes bits, no row padding).  For a sample x with
+ * prediction pred:
+ *     u = rice_map((x - pred) mod 2^B)         the sample codec's mapping: 2d for d < 2^(B-1), else 2(2^B - d) - 1
+ *     glen(u) = 2*floor(log2(u + 1)) + 1       the Elias-gamma length of u + 1 (u + 1 formed in 32 bits): an integer proxy for code
+ *                                              length that needs no Rice parameter.  glen(0) = 1, glen(1) = glen(2) = 3,
+ *                                              glen(255) = 17, glen(65535) = 33.
+ * For every pair t = 1 .. nframes-1, stats_dev[3*(t-1) ..] receives three uint64:
+ *     moving      the pixels with at least one sample where |x_t[c] - x_{t-1}[c]| > tolerance -- the true unsigned difference, as in the
+ *                 hold: 16-bit samples 0 and 0x8000 are 32768 apart
+ *     inter_bits  the sum over the moving pixels, and over all their samples, of glen(u) with pred = x_{t-1}
+ *     intra_bits  the sum over all samples of frame t of glen(u) with the type-3 predictor: the same channel of the pixel to the left,
+ *                 of the pixel above in column 0, and 0 for the first pixel
+ * Frame t is a CUT iff inter_bits + moving > intra_bits (one bit per moving pixel for the mask): an integer rule without a tunable
+ * constant, applied by the caller (container.cut_frames).  Deterministic: the kernels write per-wave partial sums into scratch the
+ * context keeps and a second kernel folds them; no atomics.  Asynchronous on the context's stream; every frame is read once.  Frames
+ * whose base and stride are multiples of 16 go through 16-byte loads, any other sample-aligned layout, the last (width*height) % 16
+ * pixels and frames of fewer than 16 pixels through a per-pixel kernel.
+ * nframes < 2: RBF_OK, nothing is launched.  RBF_EINVAL: channels outside 1..4, sample_bytes not 1 or 2, a null pointer, frames_dev or
+ * frame_stride_bytes not a multiple of sample_bytes, stats_dev not a multiple of 8, frame_stride_bytes < width*height*channels*
+ * sample_bytes.  RBF_ERANGE: tolerance >= 2^B.  Everything is checked before anything is launched. */
+int rbf_cut_stats(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                  uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                  uint32_t tolerance, uint64_t *stats_dev);   /* 3 * (nframes - 1) uint64, device */
+
 #ifdef __cplusplus
 }
 #endif

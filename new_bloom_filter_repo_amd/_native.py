@@ -98,6 +98,7 @@ _PROTOS = {
     "rbf_rice_encode_inter": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64,
                                      ctypes.POINTER(_u64)]),
     "rbf_rice_apply_inter": (_int, [_vp, _vp, ctypes.POINTER(_u64), _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "rbf_cut_stats": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_frame_digest_batch": (_int, [_vp, _vp, _u64, _u32, _u64, _vp]),
     "rbf_frame_digest_host": (_u64, [_vp, _u64]),
 }

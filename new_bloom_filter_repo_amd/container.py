@@ -118,3 +118,17 @@ def blocks_off_keyframes(blocks, first_index, keyframe_interval):
     A near-lossless call (max_error > 0) needs this list to be empty: a block's frames are held against the block's own first frame, so a
     block that starts inside a run would need the held state of the block in front of it, which lives in another lane's coder."""
     return [b for b in blocks if not is_keyframe(b[0], first_index, keyframe_interval)]
+
+
+def cut_frames(stats, run_starts=()):
+    """The scene-cut rule on the statistics of a block (GopCoder.cut_stats: one row (moving, inter_bits, intra_bits) per pair, row j - 1
+    for frame j of the block): frame j is a cut iff inter_bits + moving > intra_bits -- coding it against its predecessor, at one mask bit
+    per moving pixel, would cost more than coding it on its own.  Integers only, no tunable constant.  Returns the block indices j >= 1,
+    ascending, that are cuts and not run starts (keyframes of the stream) already."""
+    known = {int(t) for t in run_starts}
+    cuts = []
+    for j, row in enumerate(stats, start=1):
+        moving, inter, intra = (int(v) for v in row)
+        if inter + moving > intra and j not in known:
+            cuts.append(j)
+    return cuts

@@ -18,6 +18,7 @@
 #include "rbf_kernels_witness.h"
 #include "rbf_kernels_pack.h"
 #include "rbf_kernels_digest.h"
+#include "rbf_kernels_cut.h"
 #include "rbf_rice_host.h"
 
 #include <cmath>
@@ -1598,6 +1599,52 @@ int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stre
                                ctx->rice_err.p);
         });
     }
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+// ---- scene cuts: the statistics that decide whether a frame is cheaper as a keyframe (rbf_kernels_cut.h); read-only on the frames
+int rbf_cut_stats(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                  uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                  uint32_t tolerance, uint64_t *stats_dev)
+{
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    if (int r = check_layout(l, nframes, rules)) return r;
+    if (tolerance >> (8 * sample_bytes)) return fail(RBF_ERANGE, "tolerance %u does not fit a %u-bit sample", tolerance, 8 * sample_bytes);
+    if (nframes < 2) return RBF_OK;                               // no pair
+    if (!frames_dev || !stats_dev) return fail(RBF_EINVAL, "null device pointer");
+    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    if ((uintptr_t)stats_dev % 8) return fail(RBF_EINVAL, "stats_dev must be 8-byte aligned");
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    // lane tiles of 16 pixels through 16-byte loads where the layout allows them, the per-pixel kernel for everything else
+    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
+    const uint64_t lanes = vec ? n / CUT_LANE_PIXELS : 0, first_px = lanes * CUT_LANE_PIXELS;
+    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
+    if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    const uint32_t pairs = nframes - 1;
+    const uint64_t rows = (bx_lanes + bx_px) * WG_WAVES;          // a row of three sums per wave and pair; every row is written by every call
+    if (int r = ctx->cut_partials.reserve((size_t)pairs * rows * CUT_STATS * 4)) return r;
+    const uint8_t *const frames = (const uint8_t *)frames_dev;
+    uint32_t *const partials = ctx->cut_partials.p;
+    if (lanes) {
+        const dim3 grid((uint32_t)bx_lanes), block(WG_THREADS);
+#define RBF_CUT(S, C) hipLaunchKernelGGL((k_cut_stats<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, nframes, lanes, width, tolerance, partials, rows)
+        if (sample_bytes == 1) { if (channels == 1) RBF_CUT(uint8_t, 1); else if (channels == 2) RBF_CUT(uint8_t, 2); else if (channels == 3) RBF_CUT(uint8_t, 3); else RBF_CUT(uint8_t, 4); }
+        else { if (channels == 1) RBF_CUT(uint16_t, 1); else if (channels == 2) RBF_CUT(uint16_t, 2); else if (channels == 3) RBF_CUT(uint16_t, 3); else RBF_CUT(uint16_t, 4); }
+#undef RBF_CUT
+    }
+    if (first_px < n)
+        by_sample_width(sample_bytes, [&](auto s) {
+            hipLaunchKernelGGL(k_cut_stats_px<decltype(s)>, dim3((uint32_t)bx_px), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes,
+                               nframes, first_px, n, width, channels, tolerance, partials, rows, bx_lanes * WG_WAVES);
+        });
+    hipLaunchKernelGGL(k_cut_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, partials, rows, stats_dev);
     HIP_TRY(hipGetLastError());
     return RBF_OK;
 }

@@ -488,19 +488,22 @@ def gather_device_records(records, device, dst=0, group=None, max_records=None, 
 
 
 def encode_video_sharded(frames, first_index, nframes_total, keyframe_interval=30, ctx=None, dst=0, group=None, mask_channels="luma",
-                         sample_codec="zlib"):
+                         sample_codec="zlib", scene_cuts=False):
     """Code this rank's shard and gather the container records on rank `dst`.
 
     frames: the frames this rank READS, i.e. global indices [halo_start(start), stop) where
     (start, stop) = shard_range(nframes_total, world, rank); first_index = halo_start(start).
     mask_channels: "luma" or "all"; sample_codec: "zlib" or "rice" (ImprovedVideoCompressor's keywords; every rank must pass the same).
+    scene_cuts: ImprovedVideoCompressor's keyword too: a frame that is cheaper as a keyframe becomes one.  The decision for a frame depends
+    only on it and its predecessor -- which every shard has, as its halo frame at the latest -- so the shards agree with a single process.
     Returns the container bytes on dst (container.write), None elsewhere."""
     import torch.distributed as dist
     from . import container
     from .video_compressor import ImprovedVideoCompressor
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     start, stop = shard_range(nframes_total, world, rank)
-    comp = ImprovedVideoCompressor(keyframe_interval=keyframe_interval, ctx=ctx, mask_channels=mask_channels, sample_codec=sample_codec)
+    comp = ImprovedVideoCompressor(keyframe_interval=keyframe_interval, ctx=ctx, mask_channels=mask_channels, sample_codec=sample_codec,
+                                   scene_cuts=scene_cuts)
     try:
         coded = comp.encode_range(frames, first_index, start, stop)      # blocks of two keyframe intervals over two GPU lanes; the lanes' memory is released inside
     finally:

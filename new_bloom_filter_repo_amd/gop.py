@@ -347,6 +347,24 @@ class GopCoder:
         return codec.encode_inter(self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W, self.H,
                                   self.C, self.sb, self.masks.ptr, self.mask_stride, ones)
 
+    def cut_stats(self, gop=0, tolerance=0):
+        """The scene-cut statistics of resident GOP `gop` (rbf_cut_stats, include/rbf.h): a (pairs, 3) uint64 array, row f = (moving,
+        inter_bits, intra_bits) of frame f + 1 against frame f; container.cut_frames applies the rule.  Read-only, ONE launch sequence over
+        the block AS IT IS NOW and one download of 24 bytes per pair: the surface calls it directly after load_frames(), before any hold
+        has rewritten the block -- after an encode() with max_error > 0 it would describe the held frames.  tolerance: a pixel counts as
+        moving when a sample differs by more than this from the frame before (what a hold of that bound would keep still is not counted)."""
+        if self.frames is None:
+            raise ValueError("cut_stats needs the interleaved frames (keep_interleaved=True)")
+        assert 0 <= gop < self.resident_gops
+        if self.pairs < 1:
+            return np.zeros((0, 3), dtype=np.uint64)
+        if getattr(self, "_cut_stats", None) is None:
+            self._cut_stats = self._alloc(24 * self.pairs)
+        nat.check(nat.lib().rbf_cut_stats(self.ctx.handle, self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+                                          self.H, self.C, self.sb, int(tolerance), self._cut_stats.ptr))
+        self.ctx.sync()
+        return self._cut_stats.numpy(self.ctx, 24 * self.pairs)[:24 * self.pairs].view(np.uint64).reshape(self.pairs, 3).copy()
+
     def frame_digests(self):
         """FD1 of the F resident frames of the GOP encode() last coded (integrity.py): ONE rbf_frame_digest_batch over the block -- bytes the
         hold and the mask stage have just read -- and one download of 8 F bytes; uint64[F].  Call it after encode(): with max_error > 0 the

@@ -150,6 +150,7 @@ class _LanePool:
 class _BlockRecords(list):
     """What _encode_block returns: the per-pair list, with the block's frame digests (uint64 per frame of the block, or None)."""
     digests = None
+    cuts = ()                                    # scene_cuts=True: the block indices the cut rule made run starts
 
 
 def _union_seconds(intervals):
@@ -177,8 +178,8 @@ class ImprovedVideoCompressor:
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
-                 frame_digests=False, verify_digests=True, hold_mode="first"):
-        """Reference signature (improved_video_compressor.py:318-327) plus eleven keyword-only extras:
+                 frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False):
+        """Reference signature (improved_video_compressor.py:318-327) plus twelve keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -214,7 +215,25 @@ class ImprovedVideoCompressor:
         block; frames that reach the container from the caller's arrays (keyframes, the frame-by-frame route) by the host twin.
         verify_digests: True (default) -- decompress_video checks a container's digests, inter-frames on the GPU from the block they are
         rebuilt in, and raises IntegrityError at the first frame (in stream order) that does not match; False -- the trailer is parsed and
-        ignored.  A container without one decodes as ever.  last_integrity says how many frames were checked, and where."""
+        ignored.  A container without one decodes as ever.  last_integrity says how many frames were checked, and where.
+        scene_cuts: False (default) -- frame t is a keyframe iff t % keyframe_interval == 0, whatever is in it; the container is today's,
+        byte for byte.  True -- a frame that is cheaper coded on its own than against its predecessor (a scene cut: its mask would be all
+        ones and its "changed values" the difference of two unrelated pictures) becomes a keyframe as well.  The decision is made on the GPU
+        from the block's resident frames right after their upload (GopCoder.cut_stats: rbf_cut_stats, one pass that reads every frame
+        once; container.cut_frames: inter_bits + moving > intra_bits, integers, no tunable constant) and the cut frames join the block's
+        run starts, so the hold, the mask stage and the Bloom kernels treat them exactly like the rule's keyframes.  With max_error > 0 a
+        pixel the hold will keep still is not counted as moving (tolerance max_error for hold_mode="first", 2 * max_error for
+        "lookahead"), and a cut frame is exact like every keyframe.  The keyframe rule itself is unchanged, and decompress_video derives
+        its runs from the record types: a fresh default compressor decodes the container.  Needs a resident block to look at: not with
+        gop_batching=False, inter_frames=False or keyframe_interval=1; a block the GPU cannot batch is coded as without the keyword.
+        last_scene_cuts lists the cut frames (global indices, ascending) of the last encode_range."""
+        self.scene_cuts = bool(scene_cuts)
+        self.last_scene_cuts = []                # scene_cuts=True: the frames the last encode_range made keyframes because they are cuts
+        if self.scene_cuts:
+            if not gop_batching:
+                raise ValueError("scene_cuts=True needs gop_batching=True: the frame-by-frame route has no resident block to look at")
+            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
+                raise ValueError("scene_cuts=True acts on inter-frames: not with inter_frames=False or keyframe_interval=1")
         if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
             raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
         self.max_error = int(max_error)
@@ -359,6 +378,8 @@ class ImprovedVideoCompressor:
         ONE rbf_encode_runs launch sequence for all the runs, ONE exact-size download of the packed record (rbf_pack_records), one
         batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.  With
         frame_digests the block's frames are digested where they lie, after the hold (GopCoder.frame_digests): the list's `digests`.
+        With scene_cuts the block is looked at right after its upload (GopCoder.cut_stats) and the frames the rule calls cuts are
+        added to the run starts: the list's `cuts`.
         lane: the context and coders to use (default: lane 0); busy: list that receives the (start, end) time of this block's GPU work.
         Returns a list of futures / None per pair (None = needs a keyframe, or is one), or None when the block cannot be batched
         (mixed shapes or dtypes)."""
@@ -381,6 +402,13 @@ class ImprovedVideoCompressor:
         block = _as_block(data)
         t1 = time.perf_counter()
         coder.load_frames(block)                 # (synchronous: the frames are pageable host memory)
+        t_up = time.perf_counter()
+        cuts = []
+        if self.scene_cuts:                      # before any hold rewrites the block; a pixel the hold will keep still is not moving
+            tol = 0 if not self.max_error else self.max_error if self.hold_mode == "first" else 2 * self.max_error
+            cuts = container.cut_frames(coder.cut_stats(tolerance=min(tol, (1 << (8 * sb)) - 1)), run_starts)
+            if cuts:
+                coder.set_run_starts(sorted(set(run_starts) | set(cuts)))
         t2 = time.perf_counter()
         coder.encode()
         if self.profile_stages:
@@ -397,12 +425,15 @@ class ImprovedVideoCompressor:
         if rice:                                 # the value fields: every pair's residual stream in one launch sequence
             values = coder.rice_streams([r["ones"] for r in res], lane.sample_coder())
         t5 = time.perf_counter()
-        self._tm_add(stack=t1 - t0, upload=t2 - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
+        self._tm_add(stack=t1 - t0, upload=t_up - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
+        if self.scene_cuts:
+            self._tm_add(cut_stats=t2 - t_up)    # (one launch sequence, a wait and 24 bytes per pair)
         if busy is not None:
             busy.append((t1, t5))
         n = H * W
         out = _BlockRecords()
         out.digests = block_digests
+        out.cuts = tuple(cuts)
         broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
         for f, r in enumerate(res):
             if r.get("skipped"):                 # the pair in front of a keyframe
@@ -436,7 +467,7 @@ class ImprovedVideoCompressor:
     def encode_range(self, frames, first_index, start, stop, inter_frames=True, release=True):
         """[(type, record)] for the frames with global indices [start, stop); frames[i] is global frame
         first_index + i (a shard passes its halo frame too, dist.halo_start).  Frame t is a keyframe iff
-        t % keyframe_interval == 0; the inter-frames are coded in blocks of up to `block_frames` consecutive frames --
+        t % keyframe_interval == 0 -- or, with scene_cuts, a cut (self.last_scene_cuts) --; the inter-frames are coded in blocks of up to `block_frames` consecutive frames --
         several GOPs per block, ONE launch sequence on the GPU per block, cut at the keyframes (plan_range).  The blocks alternate over
         `gpu_lanes` contexts, each block on its own host thread; the host's zlib-9 (keyframes: four jobs each; changed values:
         one job per frame) runs on `num_threads` threads under all of it.  release: return the lanes' device memory as soon as the last
@@ -458,6 +489,7 @@ class ImprovedVideoCompressor:
                                  "on a keyframe" % (self.max_error, off[0][0], self.block_frames, I))
         want = self.frame_digests
         digests = {}                             # frame -> its digest, or the future of the host twin's
+        scene_cuts = []
         in_block = {u for lo, end, _ in blocks for u in range(lo, end)} if self.gop_batching else set()
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
@@ -503,10 +535,12 @@ class ImprovedVideoCompressor:
                 # from the block too.  Not so a frame that falls back to a keyframe with max_error > 0: its record codes the original,
                 # the block holds the held frame -- the host twin digests the original.
                 bd = getattr(inter, "digests", None)
+                cut = set(getattr(inter, "cuts", ()))                        # a cut frame is a run start of its block like a rule keyframe
+                scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
                 digest_of(lo, bd, 0)
                 for j in range(1, len(seg)):
                     u = lo + j
-                    if is_keyframe(u, first_index, I):
+                    if is_keyframe(u, first_index, I) or j in cut:
                         key(u)
                         digest_of(u, bd, j)
                         continue
@@ -534,6 +568,7 @@ class ImprovedVideoCompressor:
                 records[u] = (ty, fut() if ty == KEY else fut.result())
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
             self.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (digests[u] for u in range(start, stop))] if want else None
+        self.last_scene_cuts = sorted(scene_cuts)
         _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
         return [records[u] for u in range(start, stop)]
@@ -613,6 +648,8 @@ class ImprovedVideoCompressor:
         if self.max_error:
             results["max_error"] = self.max_error
             results["hold_mode"] = self.hold_mode
+        if self.scene_cuts:
+            results["scene_cuts"] = list(self.last_scene_cuts)
         if self.verbose:
             print("\\nCompression Results:")
             print(f"Original Size: {original_size / (1024 * 1024):.2f} MB")
