@@ -233,6 +233,30 @@ int rbf_temporal_lookahead_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_s
                                 uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                                 uint32_t max_error, const uint8_t *run_starts);
 
+/* ---- A1, near-lossless: a bound per sample ---------------------------------------------------------- */
+/* The two calls above with a BOUND FRAME in place of max_error: bounds_dev is one dense frame of width*height*channels samples of
+ * sample_bytes on the device, E[p][c] = the bound of sample c of pixel p, in the frames' own layout and sample type (so every bound
+ * fits the sample width by construction).  The same arguments, layout, runs and checks otherwise; the rules are the scalar ones with
+ * max_error replaced by E[p][c]:
+ *     Hold:       y_t = y_{t-1} if |x_t[c] - y_{t-1}[c]| <= E[p][c] for EVERY sample c of pixel p, else y_t = x_t (the whole pixel).
+ *     Look-ahead: the windows are [max(0, x - E[p][c]), min(M, x + E[p][c])]; the anchored segment, the greedy stabbing,
+ *                 v[c] = clamp(prev[c], lo[c], hi[c]) and the segment starts are unchanged.
+ * What carries over: true unsigned differences (16-bit 0 and 0x8000 are 32768 apart); a run's first frame is never written;
+ * |y_t - x_t| <= E[p][c] for every sample of every frame; a pixel whose bounds are all 0 is coded exactly, whatever its neighbours'
+ * bounds; the hold is idempotent, the look-ahead is NOT (once per uploaded block) and never updates a pixel more often than the hold;
+ * deterministic (no atomics); asynchronous on the context's stream; timed under RBF_K_HOLD.  The bound frame is only read: a lane loads
+ * its tile of it once per run, 1 / (run length) of the frames' traffic.
+ * bounds_dev's alignment rules are the frames' own: when the frames' base and stride AND bounds_dev are multiples of 16 (look-ahead: 8)
+ * the lane tiles run, anything sample-aligned goes through the per-pixel kernels.
+ * An all-zero bound frame is legal and leaves the block as it is (the kernels run).  nframes < 2: RBF_OK, nothing is launched.
+ * The error codes are those of the scalar calls; a NULL bounds_dev, or one that is not a multiple of sample_bytes, is RBF_EINVAL. */
+int rbf_temporal_hold_runs_map(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                               uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                               const void *bounds_dev, const uint8_t *run_starts);
+int rbf_temporal_lookahead_runs_map(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                                    uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                                    const void *bounds_dev, const uint8_t *run_starts);
+
 /* ---- A1, BGR input  (cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY), :794-795) --------------------- */
 /* gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15 per pixel -- OpenCV 4.x's integer path for 8- and
  * 16-bit samples; samples 0,1,2 of a pixel are B,G,R (further channels are ignored).  gray_dev receives
@@ -533,6 +557,28 @@ uint64_t rbf_frame_digest_host(const void *bytes, uint64_t nbytes);
 int rbf_cut_stats(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
                   uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                   uint32_t tolerance, uint64_t *stats_dev);   /* 3 * (nframes - 1) uint64, device */
+
+/* ---- quality report: what does a coded block differ from its originals by? ------------------------------------------------------- */
+/* Read-only, on two resident blocks of nframes dense interleaved frames of one geometry (the layout of rbf_temporal_hold_runs): A, the
+ * originals, frame f at a_dev + f*a_stride_bytes, and B, the coded frames, at b_dev + f*b_stride_bytes.  rows_host (HOST, nframes rows)
+ * receives for frame f, over all its width*height*channels samples, with the true unsigned difference of the hold:
+ *     sse         the sum of (a - b)^2, exact (64-bit integers)
+ *     differing   the samples with a != b
+ *     over_bound  the samples with |a - b| > their bound: E[p][c] when bounds_dev is a bound frame (the bound frame of
+ *                 rbf_temporal_hold_runs_map), the scalar `bound` for every sample when bounds_dev is NULL
+ *     max_abs     the largest |a - b|
+ * so that MSE = sse / samples and PSNR = 10 log10((2^B - 1)^2 / MSE) are the caller's to form.  Deterministic: the kernels write
+ * per-wave partial sums into scratch the context keeps and a second kernel folds them; no atomics.  BLOCKS until the rows are on the
+ * host.  Blocks and bounds whose bases and strides are multiples of 16 go through 16-byte loads, any other sample-aligned layout and the
+ * last (width*height) % 16 pixels of a frame through a per-pixel kernel.  Not timed: there is no RBF_K_ id for it, as for rbf_cut_stats.
+ * nframes == 0: RBF_OK, nothing is launched.  RBF_EINVAL: channels outside 1..4, sample_bytes not 1 or 2, a null a_dev, b_dev or
+ * rows_host, a base, stride or bounds_dev that is not a multiple of sample_bytes, a stride < width*height*channels*sample_bytes (with
+ * nframes >= 2).  RBF_ERANGE: bound >= 2^B with bounds_dev NULL; more than 2^31 samples per frame.  Everything is checked before anything
+ * is launched. */
+typedef struct { uint64_t sse, differing, over_bound; uint32_t max_abs, reserved; } rbf_error_row;
+int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, const void *b_dev, uint64_t b_stride_bytes,
+                    uint32_t nframes, uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                    const void *bounds_dev, uint32_t bound, rbf_error_row *rows_host);
 
 #ifdef __cplusplus
 }

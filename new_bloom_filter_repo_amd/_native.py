@@ -26,6 +26,9 @@ class FilterParams(ctypes.Structure):
     _fields_ = [("m", ctypes.c_uint32), ("floor_k", ctypes.c_uint32), ("threshold", ctypes.c_uint64)]
 
 
+ERROR_ROW = np.dtype([("sse", "<u8"), ("differing", "<u8"), ("over_bound", "<u8"), ("max_abs", "<u4"), ("reserved", "<u4")])     # rbf_error_row
+
+
 class Seeds(ctypes.Structure):
     _fields_ = [("h1", ctypes.c_uint64), ("h2", ctypes.c_uint64), ("act", ctypes.c_uint64)]
 
@@ -76,6 +79,8 @@ _PROTOS = {
     "rbf_residual_mask_batch_ex": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32, _u32, _i32, _i32p, _vp, _u64, _vp, _u32]),
     "rbf_temporal_hold_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_temporal_lookahead_runs": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "rbf_temporal_hold_runs_map": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "rbf_temporal_lookahead_runs_map": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "rbf_record_max_bytes": (_u64, [_u32, _u64]),
     "rbf_pack_records": (_int, [_vp, _u32, _u64, ctypes.POINTER(FilterParams), ctypes.POINTER(ctypes.c_double),
                                 _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64]),
@@ -99,6 +104,7 @@ _PROTOS = {
                                      ctypes.POINTER(_u64)]),
     "rbf_rice_apply_inter": (_int, [_vp, _vp, ctypes.POINTER(_u64), _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
     "rbf_cut_stats": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "rbf_error_stats": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
     "rbf_frame_digest_batch": (_int, [_vp, _vp, _u64, _u32, _u64, _vp]),
     "rbf_frame_digest_host": (_u64, [_vp, _u64]),
 }

@@ -1,5 +1,5 @@
 """The video container, its record types and the layout of a stream: which frames are keyframes, where the encoder's blocks and the
-decoder's runs start and end (no numpy, no GPU).
+decoder's runs start and end, and the bound frame of a near-lossless call (no GPU; numpy only in bounds_frame).
 
 All-keyframe streams are written exactly as the reference does -- 'BFVC' | <I frames | (<I len | record)*
 (improved_video_compressor.py:398-406) -- so either implementation reads them.  Streams with any other record use magic 'BFV2' and prefix
@@ -118,6 +118,62 @@ def blocks_off_keyframes(blocks, first_index, keyframe_interval):
     A near-lossless call (max_error > 0) needs this list to be empty: a block's frames are held against the block's own first frame, so a
     block that starts inside a run would need the held state of the block in front of it, which lives in another lane's coder."""
     return [b for b in blocks if not is_keyframe(b[0], first_index, keyframe_interval)]
+
+
+def bounds_frame(error_bounds, shape=None, dtype=None):
+    """The BOUND FRAME of a near-lossless call with a bound per sample: an array of exactly a frame's `shape` ((H, W) or (H, W, C)) and
+    `dtype` (uint8 / uint16) whose entry is the largest error its sample may be coded with -- the only form the layers below the surface
+    see (GopCoder(error_bounds=...), rbf_temporal_hold_runs_map).  error_bounds is one of
+      a sequence of C non-negative integers          one bound per channel (C = 1 for (H, W) frames)
+      an integer array of shape (H, W)               one bound per pixel, for all of its samples
+      an integer array of shape (H, W, C)            one bound per sample
+    ValueError for anything else: a str, a scalar, floats, bools, negative values, values that do not fit the sample width, a shape that
+    does not fit the frames.  shape=None: only what can be said without a frame is checked (the constructors do that) and the bounds come
+    back as an int64 array.  (The one function of this module that needs numpy; no native library.)"""
+    import numpy as np
+    if isinstance(error_bounds, (str, bytes, bytearray)) or np.ndim(error_bounds) == 0:
+        raise ValueError("error_bounds must be a sequence of per-channel bounds or an (H, W) / (H, W, C) integer array, got %r" % (error_bounds,))
+    if isinstance(error_bounds, (list, tuple)) and any(isinstance(v, (bool, np.bool_)) for v in error_bounds):
+        raise ValueError("error_bounds must be integers, got a bool in %r" % (error_bounds,))
+    try:
+        e = np.asarray(error_bounds)
+    except ValueError:
+        raise ValueError("error_bounds is not a rectangular array") from None
+    if e.dtype.kind not in "iu":
+        raise ValueError("error_bounds must be integers, got dtype %s" % e.dtype)
+    if not 1 <= e.ndim <= 3 or e.size == 0:
+        raise ValueError("error_bounds must have one, two or three dimensions, got shape %r" % (e.shape,))
+    e = e.astype(np.int64) if e.dtype != np.uint64 else e
+    if int(e.min()) < 0:
+        raise ValueError("error_bounds must be non-negative, got %d" % int(e.min()))
+    if shape is None:
+        return e
+    shape, dtype = tuple(int(s) for s in shape), np.dtype(dtype)
+    if dtype not in (np.uint8, np.uint16) or len(shape) not in (2, 3):
+        raise ValueError("a bound frame is an (H, W) or (H, W, C) frame of uint8 or uint16, got %r of %s" % (shape, dtype))
+    top = int(np.iinfo(dtype).max)
+    if int(e.max()) > top:
+        raise ValueError("error_bounds %d does not fit a %d-bit sample" % (int(e.max()), 8 * dtype.itemsize))
+    C = shape[2] if len(shape) == 3 else 1
+    if e.ndim == 1:
+        if e.shape[0] != C:
+            raise ValueError("error_bounds has %d per-channel bounds, the frames have %d channel(s)" % (e.shape[0], C))
+        e = e if len(shape) == 3 else e[0]
+    elif e.shape == shape[:2] and len(shape) == 3:
+        e = e[:, :, None]
+    elif e.shape != shape:
+        raise ValueError("error_bounds of shape %r does not fit frames of shape %r" % (e.shape, shape))
+    out = np.empty(shape, dtype=dtype)
+    out[...] = e
+    return out
+
+
+def uniform_bound(bound_frame):
+    """d when every entry of the bound frame equals d, else None: such a frame is today's max_error=d, and the surface codes it through
+    the scalar calls -- the container is byte for byte that of max_error=d."""
+    flat = bound_frame.reshape(-1)
+    d = int(flat[0])
+    return d if bool((flat == flat[0]).all()) else None
 
 
 def cut_frames(stats, run_starts=()):

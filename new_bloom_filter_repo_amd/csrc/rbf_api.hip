@@ -19,6 +19,7 @@
 #include "rbf_kernels_pack.h"
 #include "rbf_kernels_digest.h"
 #include "rbf_kernels_cut.h"
+#include "rbf_kernels_error.h"
 #include "rbf_rice_host.h"
 
 #include <cmath>
@@ -943,30 +944,52 @@ int rbf_residual_mask_batch_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t fr
     return residual_mask_impl(ctx, MaskArgs{frames_dev, l, nframes, thr_floor, thr_floors, masks_dev, mask_stride_bytes, ones_dev, mask_channels}, true);
 }
 
-// ---- A1, near-lossless: the temporal hold in front of the mask stage
-int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
-                           uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
-                           uint32_t max_error, const uint8_t *run_starts)
+// ---- A1, near-lossless: the temporal hold in front of the mask stage (rbf_kernels_hold.h) and the look-ahead hold
+// (rbf_kernels_lookahead.h), each with one bound (max_error) or with a bound per sample (bounds_dev, a frame of bounds): the four entry
+// points share their checks, their runs and their no-op cases.
+struct HoldCall {
+    void *frames_dev; uint64_t frame_stride_bytes; uint32_t nframes, width, height, channels, sample_bytes;
+    bool lookahead, map;             // the rule; map: bounds_dev instead of max_error
+    uint32_t max_error; const void *bounds_dev;
+    const uint8_t *run_starts;
+};
+
+static int temporal_hold_impl(rbf_ctx *ctx, const HoldCall &c)
 {
     if (int r = set_device(ctx)) return r;
+    const uint32_t sample_bytes = c.sample_bytes, channels = c.channels, nframes = c.nframes, max_error = c.max_error;
+    const uint64_t frame_stride_bytes = c.frame_stride_bytes;
     const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    const FrameLayout l{c.width, c.height, (uint64_t)c.width * pixel, pixel, sample_bytes, frame_stride_bytes};
     LayoutRules rules;
     rules.samples = channels; rules.channels = true;
     if (int r = check_layout(l, nframes, rules)) return r;
-    if (max_error >> (8 * sample_bytes)) return fail(RBF_ERANGE, "max_error %u does not fit a %u-bit sample", max_error, 8 * sample_bytes);
-    if (max_error == 0 || nframes < 2) return RBF_OK;             // y = x
-    if (!frames_dev) return fail(RBF_EINVAL, "null device pointer");
-    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (c.map) {
+        if (!c.bounds_dev) return fail(RBF_EINVAL, "null bounds_dev");
+        if ((uintptr_t)c.bounds_dev % sample_bytes) return fail(RBF_EINVAL, "bounds misaligned for %u-byte samples", sample_bytes);
+        if (nframes < 2) return RBF_OK;                           // y = x
+    } else {
+        if (max_error >> (8 * sample_bytes)) return fail(RBF_ERANGE, "max_error %u does not fit a %u-bit sample", max_error, 8 * sample_bytes);
+        if (max_error == 0 || nframes < 2) return RBF_OK;         // y = x
+    }
+    if (!c.frames_dev) return fail(RBF_EINVAL, "null device pointer");
+    if ((uintptr_t)c.frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    const uint64_t n = (uint64_t)c.width * c.height, frame_bytes = n * pixel;
     if (frame_stride_bytes < frame_bytes)
         return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
-    // lane tiles of 16 pixels through 16-byte accesses where the layout allows them, the per-pixel kernel for everything else
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
-    const uint64_t lanes = vec ? n / HOLD_LANE_PIXELS : 0, first_px = lanes * HOLD_LANE_PIXELS;
+    // lane tiles of 16 pixels through 16-byte accesses (look-ahead: 8 pixels, 8-byte accesses) where the layout allows them -- the frames'
+    // base and stride, and the bound frame's base --, the per-pixel kernel for everything else
+    const uint32_t lane_px = c.lookahead ? LA_LANE_PIXELS : HOLD_LANE_PIXELS, align = c.lookahead ? 8 : 16;
+    const bool vec = !ctx->knobs.force_generic && (uintptr_t)c.frames_dev % align == 0 && frame_stride_bytes % align == 0 &&
+                     (!c.map || (uintptr_t)c.bounds_dev % align == 0);
+    const uint64_t lanes = vec ? n / lane_px : 0, first_px = lanes * lane_px;
     const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
     if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
-    uint8_t *const frames = (uint8_t *)frames_dev;
+    const uint64_t bits_stride = (n + 7) / 8;                     // look-ahead, the segment-start bits: a row per frame, a byte per lane tile
+    if (c.lookahead && lanes)
+        if (int r = ctx->hold_bits.reserve((size_t)nframes * bits_stride)) return r;
+    uint8_t *const frames = (uint8_t *)c.frames_dev, *const bits = ctx->hold_bits.p;
+    const uint8_t *const bounds = (const uint8_t *)c.bounds_dev;
     HoldRuns runs{};
     uint32_t count = 0;
     auto flush = [&]() {
@@ -974,22 +997,42 @@ int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride
         LaunchTimer t(ctx, RBF_K_HOLD);
         if (lanes) {
             const dim3 grid((uint32_t)bx_lanes, count), block(WG_THREADS);
-#define RBF_HOLD(S, C) hipLaunchKernelGGL((k_temporal_hold<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, runs)
+#define RBF_HOLD(S, C)                                                                                                                           \
+    do {                                                                                                                                         \
+        if (!c.lookahead && !c.map)                                                                                                              \
+            hipLaunchKernelGGL((k_temporal_hold<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, runs);        \
+        else if (!c.lookahead)                                                                                                                   \
+            hipLaunchKernelGGL((k_hold_map<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bounds, runs);                \
+        else if (!c.map)                                                                                                                         \
+            hipLaunchKernelGGL((k_temporal_lookahead<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, bits, bits_stride, runs); \
+        else                                                                                                                                     \
+            hipLaunchKernelGGL((k_lookahead_map<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bounds, bits, bits_stride, runs); \
+        if (c.lookahead)                                                                                                                         \
+            hipLaunchKernelGGL((k_lookahead_fill<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bits, bits_stride, runs); \
+    } while (0)
             if (sample_bytes == 1) { if (channels == 1) RBF_HOLD(uint8_t, 1); else if (channels == 2) RBF_HOLD(uint8_t, 2); else if (channels == 3) RBF_HOLD(uint8_t, 3); else RBF_HOLD(uint8_t, 4); }
             else { if (channels == 1) RBF_HOLD(uint16_t, 1); else if (channels == 2) RBF_HOLD(uint16_t, 2); else if (channels == 3) RBF_HOLD(uint16_t, 3); else RBF_HOLD(uint16_t, 4); }
 #undef RBF_HOLD
         }
         if (first_px < n)
             by_sample_width(sample_bytes, [&](auto s) {
-                hipLaunchKernelGGL(k_temporal_hold_px<decltype(s)>, dim3((uint32_t)bx_px, count), dim3(WG_THREADS), 0, ctx->stream, frames,
-                                   frame_stride_bytes, first_px, n, channels, max_error, runs);
+                using S = decltype(s);
+                const dim3 grid((uint32_t)bx_px, count), block(WG_THREADS);
+                if (!c.lookahead && !c.map)
+                    hipLaunchKernelGGL(k_temporal_hold_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, max_error, runs);
+                else if (!c.lookahead)
+                    hipLaunchKernelGGL(k_hold_map_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, bounds, runs);
+                else if (!c.map)
+                    hipLaunchKernelGGL(k_temporal_lookahead_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, max_error, runs);
+                else
+                    hipLaunchKernelGGL(k_lookahead_map_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, bounds, runs);
             });
         count = 0;
     };
     // the runs: frame 0 and every marked frame start one; a run of one frame has nothing to hold
     for (uint32_t a = 0; a < nframes;) {
         uint32_t b = a + 1;
-        while (b < nframes && !(run_starts && run_starts[b])) ++b;
+        while (b < nframes && !(c.run_starts && c.run_starts[b])) ++b;
         if (b - a >= 2) {
             runs.first[count] = a; runs.len[count] = b - a;
             if (++count == HOLD_MAX_RUNS) flush();
@@ -1001,68 +1044,32 @@ int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride
     return RBF_OK;
 }
 
-// ---- A1, near-lossless: the look-ahead hold (rbf_kernels_lookahead.h) -- the same checks, runs and no-op cases as the hold above
+int rbf_temporal_hold_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                           uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                           uint32_t max_error, const uint8_t *run_starts)
+{
+    return temporal_hold_impl(ctx, HoldCall{frames_dev, frame_stride_bytes, nframes, width, height, channels, sample_bytes, false, false, max_error, nullptr, run_starts});
+}
+
 int rbf_temporal_lookahead_runs(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
                                 uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                                 uint32_t max_error, const uint8_t *run_starts)
 {
-    if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, nframes, rules)) return r;
-    if (max_error >> (8 * sample_bytes)) return fail(RBF_ERANGE, "max_error %u does not fit a %u-bit sample", max_error, 8 * sample_bytes);
-    if (max_error == 0 || nframes < 2) return RBF_OK;             // y = x
-    if (!frames_dev) return fail(RBF_EINVAL, "null device pointer");
-    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
-    // lane tiles of 8 pixels through 8-byte accesses where the layout allows them, the per-pixel kernel for everything else
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 8 == 0 && frame_stride_bytes % 8 == 0;
-    const uint64_t lanes = vec ? n / LA_LANE_PIXELS : 0, first_px = lanes * LA_LANE_PIXELS;
-    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
-    if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
-    const uint64_t bits_stride = (n + 7) / 8;                     // the segment-start bits: a row per frame, a byte per lane tile
-    if (lanes)
-        if (int r = ctx->hold_bits.reserve((size_t)nframes * bits_stride)) return r;
-    uint8_t *const frames = (uint8_t *)frames_dev, *const bits = ctx->hold_bits.p;
-    HoldRuns runs{};
-    uint32_t count = 0;
-    auto flush = [&]() {
-        if (!count) return;
-        LaunchTimer t(ctx, RBF_K_HOLD);
-        if (lanes) {
-            const dim3 grid((uint32_t)bx_lanes, count), block(WG_THREADS);
-#define RBF_LA(S, C)                                                                                                                             \
-    do {                                                                                                                                         \
-        hipLaunchKernelGGL((k_temporal_lookahead<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, bits, bits_stride, runs); \
-        hipLaunchKernelGGL((k_lookahead_fill<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bits, bits_stride, runs);   \
-    } while (0)
-            if (sample_bytes == 1) { if (channels == 1) RBF_LA(uint8_t, 1); else if (channels == 2) RBF_LA(uint8_t, 2); else if (channels == 3) RBF_LA(uint8_t, 3); else RBF_LA(uint8_t, 4); }
-            else { if (channels == 1) RBF_LA(uint16_t, 1); else if (channels == 2) RBF_LA(uint16_t, 2); else if (channels == 3) RBF_LA(uint16_t, 3); else RBF_LA(uint16_t, 4); }
-#undef RBF_LA
-        }
-        if (first_px < n)
-            by_sample_width(sample_bytes, [&](auto s) {
-                hipLaunchKernelGGL(k_temporal_lookahead_px<decltype(s)>, dim3((uint32_t)bx_px, count), dim3(WG_THREADS), 0, ctx->stream, frames,
-                                   frame_stride_bytes, first_px, n, channels, max_error, runs);
-            });
-        count = 0;
-    };
-    for (uint32_t a = 0; a < nframes;) {
-        uint32_t b = a + 1;
-        while (b < nframes && !(run_starts && run_starts[b])) ++b;
-        if (b - a >= 2) {
-            runs.first[count] = a; runs.len[count] = b - a;
-            if (++count == HOLD_MAX_RUNS) flush();
-        }
-        a = b;
-    }
-    flush();
-    HIP_TRY(hipGetLastError());
-    return RBF_OK;
+    return temporal_hold_impl(ctx, HoldCall{frames_dev, frame_stride_bytes, nframes, width, height, channels, sample_bytes, true, false, max_error, nullptr, run_starts});
+}
+
+int rbf_temporal_hold_runs_map(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                               uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                               const void *bounds_dev, const uint8_t *run_starts)
+{
+    return temporal_hold_impl(ctx, HoldCall{frames_dev, frame_stride_bytes, nframes, width, height, channels, sample_bytes, false, true, 0, bounds_dev, run_starts});
+}
+
+int rbf_temporal_lookahead_runs_map(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                                    uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                                    const void *bounds_dev, const uint8_t *run_starts)
+{
+    return temporal_hold_impl(ctx, HoldCall{frames_dev, frame_stride_bytes, nframes, width, height, channels, sample_bytes, true, true, 0, bounds_dev, run_starts});
 }
 
 int rbf_bgr_to_gray_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
@@ -1646,6 +1653,65 @@ int rbf_cut_stats(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_by
         });
     hipLaunchKernelGGL(k_cut_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, partials, rows, stats_dev);
     HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+// ---- quality report: what a coded block differs from its originals by (rbf_kernels_error.h); read-only on both blocks, blocks until the
+// rows are on the host
+int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, const void *b_dev, uint64_t b_stride_bytes, uint32_t nframes,
+                    uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                    const void *bounds_dev, uint32_t bound, rbf_error_row *rows_host)
+{
+    static_assert(sizeof(ErrorRow) == sizeof(rbf_error_row) && sizeof(rbf_error_row) == 32, "the kernels write the ABI's rows");
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    for (const uint64_t stride : {a_stride_bytes, b_stride_bytes}) {
+        const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, stride};
+        if (int r = check_layout(l, nframes, rules)) return r;
+    }
+    if (!bounds_dev && bound >> (8 * sample_bytes)) return fail(RBF_ERANGE, "bound %u does not fit a %u-bit sample", bound, 8 * sample_bytes);
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (n * channels > 0x80000000ull) return fail(RBF_ERANGE, "frame of %llu samples is too large", (unsigned long long)(n * channels));
+    if (nframes == 0) return RBF_OK;
+    if (!a_dev || !b_dev || !rows_host) return fail(RBF_EINVAL, "null pointer");
+    if ((uintptr_t)a_dev % sample_bytes || (uintptr_t)b_dev % sample_bytes || (uintptr_t)bounds_dev % sample_bytes)
+        return fail(RBF_EINVAL, "blocks or bounds misaligned for %u-byte samples", sample_bytes);
+    if (nframes > 1 && (a_stride_bytes < frame_bytes || b_stride_bytes < frame_bytes))
+        return fail(RBF_EINVAL, "frame stride smaller than a frame of %llu bytes", (unsigned long long)frame_bytes);
+    // lane tiles of 16 pixels through 16-byte loads where every base and stride allows them, the per-pixel kernel for everything else
+    const bool vec = !ctx->knobs.force_generic && (uintptr_t)a_dev % 16 == 0 && (uintptr_t)b_dev % 16 == 0 && (uintptr_t)bounds_dev % 16 == 0 &&
+                     (nframes == 1 || (a_stride_bytes % 16 == 0 && b_stride_bytes % 16 == 0));
+    const uint64_t lanes = vec ? n / ERR_LANE_PIXELS : 0, first_px = lanes * ERR_LANE_PIXELS;
+    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
+    const uint64_t rows = (bx_lanes + bx_px) * WG_WAVES;          // a row per wave and frame; every row is written by every call
+    if (int r = ctx->err_partials.reserve((size_t)nframes * rows * ERR_WORDS * 4)) return r;
+    if (int r = ctx->err_rows.reserve((size_t)nframes * sizeof(ErrorRow))) return r;
+    const uint8_t *const a = (const uint8_t *)a_dev, *const b = (const uint8_t *)b_dev, *const bounds = (const uint8_t *)bounds_dev;
+    uint32_t *const partials = ctx->err_partials.p;
+    if (lanes) {
+        const dim3 grid((uint32_t)bx_lanes), block(WG_THREADS);
+#define RBF_ERR(S, C)                                                                                                                            \
+    do {                                                                                                                                         \
+        if (bounds)                                                                                                                              \
+            hipLaunchKernelGGL((k_error_stats<S, C, true>), grid, block, 0, ctx->stream, a, a_stride_bytes, b, b_stride_bytes, nframes, lanes, bounds, bound, partials, rows); \
+        else                                                                                                                                     \
+            hipLaunchKernelGGL((k_error_stats<S, C, false>), grid, block, 0, ctx->stream, a, a_stride_bytes, b, b_stride_bytes, nframes, lanes, bounds, bound, partials, rows); \
+    } while (0)
+        if (sample_bytes == 1) { if (channels == 1) RBF_ERR(uint8_t, 1); else if (channels == 2) RBF_ERR(uint8_t, 2); else if (channels == 3) RBF_ERR(uint8_t, 3); else RBF_ERR(uint8_t, 4); }
+        else { if (channels == 1) RBF_ERR(uint16_t, 1); else if (channels == 2) RBF_ERR(uint16_t, 2); else if (channels == 3) RBF_ERR(uint16_t, 3); else RBF_ERR(uint16_t, 4); }
+#undef RBF_ERR
+    }
+    if (first_px < n)
+        by_sample_width(sample_bytes, [&](auto s) {
+            hipLaunchKernelGGL(k_error_stats_px<decltype(s)>, dim3((uint32_t)bx_px), dim3(WG_THREADS), 0, ctx->stream, a, a_stride_bytes, b,
+                               b_stride_bytes, nframes, first_px, n, channels, bounds, bound, partials, rows, bx_lanes * WG_WAVES);
+        });
+    hipLaunchKernelGGL(k_error_reduce, dim3(nframes), dim3(WG_THREADS), 0, ctx->stream, partials, rows, (ErrorRow *)ctx->err_rows.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rows_host, ctx->err_rows.p, (size_t)nframes * sizeof(ErrorRow), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RBF_OK;
 }
 

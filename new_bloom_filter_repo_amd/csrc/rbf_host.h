@@ -113,7 +113,9 @@ struct rbf_ctx {
     DevBuf<uint8_t> hold_bits;       // look-ahead hold (rbf_kernels_lookahead.h): the segment-start bits, nframes rows of ceil(n / 8) bytes
     DevBuf<uint64_t> digest_lvl;     // frame digests (rbf_kernels_digest.h): the block hashes of every level, per frame of the call
     DevBuf<uint32_t> cut_partials;   // scene-cut statistics (rbf_kernels_cut.h): three sums per wave and pair of the call
-    struct SharedHashTable *hash_shared = nullptr;                // the pixel-index hash table this context holds a reference to
+    DevBuf<uint32_t> err_partials;   // quality report (rbf_kernels_error.h): six words per wave and frame of the call
+    DevBuf<void> err_rows;           // ... and the folded rows (rbf_error_row), a frame each, on their way to the host
+    struct SharedHashTable *hash_shared = nullptr;               // the pixel-index hash table this context holds a reference to
     uint4 *hash_tab = nullptr;                                    // = hash_shared->table
     // host staging of encode_gop: device-visible pinned block [flag | ones...] the GPU publishes into
     uint64_t *ones_pinned = nullptr; size_t host_cap = 0;

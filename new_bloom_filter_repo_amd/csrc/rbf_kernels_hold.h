@@ -33,13 +33,20 @@ __device__ __forceinline__ uint32_t hold_exceed16(uint32_t a, uint32_t b, uint32
 
 // A dword of samples: every sample's field of the result is non-zero iff that sample of a and b differs by more than the bound.  Bytes go
 // through the 16-bit routine as their even and their odd half (the excess of a byte is < 256: it fits the byte it came from).
+// The bounds come packed per half: `de` holds those of the dword's two 16-bit samples, or of its even bytes, `dodd` those of its odd
+// bytes (unused at 16 bits).  One bound for every sample is de = dodd = bound | bound << 16.
+template <typename SAMPLE>
+__device__ __forceinline__ uint32_t hold_exceed(uint32_t a, uint32_t b, uint32_t de, uint32_t dodd)
+{
+    if (sizeof(SAMPLE) == 2) return hold_exceed16(a, b, de);
+    const uint32_t even = hold_exceed16(a & 0x00FF00FFu, b & 0x00FF00FFu, de);
+    const uint32_t odd = hold_exceed16((a >> 8) & 0x00FF00FFu, (b >> 8) & 0x00FF00FFu, dodd);
+    return even | (odd << 8);
+}
 template <typename SAMPLE>
 __device__ __forceinline__ uint32_t hold_exceed(uint32_t a, uint32_t b, uint32_t delta2)
 {
-    if (sizeof(SAMPLE) == 2) return hold_exceed16(a, b, delta2);
-    const uint32_t even = hold_exceed16(a & 0x00FF00FFu, b & 0x00FF00FFu, delta2);
-    const uint32_t odd = hold_exceed16((a >> 8) & 0x00FF00FFu, (b >> 8) & 0x00FF00FFu, delta2);
-    return even | (odd << 8);
+    return hold_exceed<SAMPLE>(a, b, delta2, delta2);
 }
 
 // the bytes of dword d that belong to pixel k of a lane's 16 pixels of PB bytes each (compile-time after unrolling)
@@ -57,14 +64,16 @@ __device__ __forceinline__ constexpr uint32_t hold_pixel_bytes(int k, int d)
 // One frame of one lane: `held` (the lane's 16 held pixels, DW dwords) against `cur` (the frame's).  On return `held` is y_t: the pixels
 // with a sample out of bound are cur's, whole -- a pixel that straddles two dwords is selected in both with its own byte masks -- and
 // the others are kept.  The decision is a select per pixel, there is no branch.
-template <typename SAMPLE, int C>
-__device__ __forceinline__ void hold_lane_step(uint32_t *held, const uint32_t *cur, uint32_t delta2)
+// MAP = false: one bound for every sample, de[0] = dodd[0] = delta2.  MAP = true: a bound per sample, de[d] / dodd[d] for dword d of the
+// tile in hold_exceed's two-bound form (k_hold_map).
+template <typename SAMPLE, int C, bool MAP = false>
+__device__ __forceinline__ void hold_lane_step(uint32_t *held, const uint32_t *cur, const uint32_t *de, const uint32_t *dodd)
 {
     constexpr int PB = C * (int)sizeof(SAMPLE), DW = (int)HOLD_LANE_PIXELS * PB / 4;
     uint32_t ex[DW], take[DW];
 #pragma unroll
     for (int d = 0; d < DW; ++d) {
-        ex[d] = hold_exceed<SAMPLE>(held[d], cur[d], delta2);
+        ex[d] = hold_exceed<SAMPLE>(held[d], cur[d], de[MAP ? d : 0], dodd[MAP ? d : 0]);
         take[d] = 0;
     }
 #pragma unroll
@@ -118,7 +127,7 @@ __global__ __launch_bounds__(WG_THREADS) void k_temporal_hold(uint8_t *__restric
     if (f0 + 2 < f1) fb.load(p + (uint64_t)(f0 + 2) * frame_stride);
     auto step = [&](const Frame &cur, Frame &nxt2, uint32_t f) {
         if (f + 2 < f1) nxt2.load(p + (uint64_t)(f + 2) * frame_stride);
-        hold_lane_step<SAMPLE, C>(held.d, cur.d, delta2);
+        hold_lane_step<SAMPLE, C>(held.d, cur.d, &delta2, &delta2);
         uint4 *const out = reinterpret_cast<uint4 *>(p + (uint64_t)f * frame_stride);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
@@ -128,6 +137,66 @@ __global__ __launch_bounds__(WG_THREADS) void k_temporal_hold(uint8_t *__restric
         }
     };
     // unrolled by three so that the rotation cur <- nxt <- nxt2 costs no register moves
+    for (uint32_t f = f0 + 1; f < f1; f += 3) {
+        step(fa, fc, f);
+        if (f + 1 < f1) step(fb, fa, f + 1);
+        if (f + 2 < f1) step(fc, fb, f + 2);
+    }
+}
+
+// k_temporal_hold with a bound per sample: `bounds` is one dense frame of bounds E[p][c] in the frames' own layout and sample type, a
+// multiple of 16 like the frames.  The lane loads its tile of it ONCE per run, next to the run's first frame -- 1 / (run length) more
+// traffic -- and keeps it in registers in the form hold_exceed wants (8 bits: the tile's even and its odd bytes, split once); the walk
+// over the run is k_temporal_hold's.  |y_t - x_t| <= E[p][c]; a pixel whose bounds are 0 is exact.
+// A sibling and not a template flag of k_temporal_hold: moving that kernel's body into a function both could share changes its register
+// allocation (measured with tools/kernel_resources.py), and the scalar kernels are to stay the code objects they were.
+template <typename SAMPLE, int C>
+__global__ __launch_bounds__(WG_THREADS) void k_hold_map(uint8_t *__restrict__ frames, uint64_t frame_stride, uint64_t lanes,
+                                                         const uint8_t *__restrict__ bounds, const HoldRuns runs)
+{
+    constexpr int PB = C * (int)sizeof(SAMPLE), DW = (int)HOLD_LANE_PIXELS * PB / 4, VEC = DW / 4;
+    static_assert(DW % 4 == 0, "a lane's pixels are whole 16-byte vectors");
+    const uint64_t lane = (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x;
+    if (lane >= lanes) return;
+    const uint32_t f0 = runs.first[blockIdx.y], f1 = f0 + runs.len[blockIdx.y];      // frames f0 + 1 .. f1 - 1 are rewritten
+    if (f1 - f0 < 2) return;
+    uint8_t *const p = frames + lane * (uint64_t)(HOLD_LANE_PIXELS * PB);
+    struct Frame {
+        uint32_t d[DW];
+        __device__ __forceinline__ void load(const uint8_t *q)
+        {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const uint4 v = reinterpret_cast<const uint4 *>(q)[i];
+                d[4 * i] = v.x; d[4 * i + 1] = v.y; d[4 * i + 2] = v.z; d[4 * i + 3] = v.w;
+            }
+        }
+    };
+    Frame held, fa, fb, fc;
+    uint32_t de[DW], dodd[sizeof(SAMPLE) == 1 ? DW : 1];
+    {
+        Frame e;
+        e.load(bounds + lane * (uint64_t)(HOLD_LANE_PIXELS * PB));
+#pragma unroll
+        for (int d = 0; d < DW; ++d) {
+            de[d] = sizeof(SAMPLE) == 2 ? e.d[d] : e.d[d] & 0x00FF00FFu;
+            if (sizeof(SAMPLE) == 1) dodd[d] = (e.d[d] >> 8) & 0x00FF00FFu;
+        }
+    }
+    held.load(p + (uint64_t)f0 * frame_stride);
+    fa.load(p + (uint64_t)(f0 + 1) * frame_stride);
+    if (f0 + 2 < f1) fb.load(p + (uint64_t)(f0 + 2) * frame_stride);
+    auto step = [&](const Frame &cur, Frame &nxt2, uint32_t f) {
+        if (f + 2 < f1) nxt2.load(p + (uint64_t)(f + 2) * frame_stride);
+        hold_lane_step<SAMPLE, C, true>(held.d, cur.d, de, sizeof(SAMPLE) == 1 ? dodd : de);
+        uint4 *const out = reinterpret_cast<uint4 *>(p + (uint64_t)f * frame_stride);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const uint32_t differs = (held.d[4 * i] ^ cur.d[4 * i]) | (held.d[4 * i + 1] ^ cur.d[4 * i + 1]) |
+                                     (held.d[4 * i + 2] ^ cur.d[4 * i + 2]) | (held.d[4 * i + 3] ^ cur.d[4 * i + 3]);
+            if (differs) out[i] = make_uint4(held.d[4 * i], held.d[4 * i + 1], held.d[4 * i + 2], held.d[4 * i + 3]);
+        }
+    };
     for (uint32_t f = f0 + 1; f < f1; f += 3) {
         step(fa, fc, f);
         if (f + 1 < f1) step(fb, fa, f + 1);
@@ -164,6 +233,42 @@ __global__ __launch_bounds__(WG_THREADS) void k_temporal_hold_px(uint8_t *__rest
                 worst = d > worst ? d : worst;
             }
         const bool upd = worst > max_error;
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) {
+            held[c] = upd ? cur[c] : held[c];
+            if (!upd && c < channels) q[c] = (SAMPLE)held[c];
+        }
+    }
+}
+
+// k_temporal_hold_px with a bound per sample: the pixel's bounds are read sample by sample from `bounds`, once per run, so any
+// sample-aligned bound frame will do.
+template <typename SAMPLE>
+__global__ __launch_bounds__(WG_THREADS) void k_hold_map_px(uint8_t *__restrict__ frames, uint64_t frame_stride, uint64_t first_pixel,
+                                                            uint64_t n, uint32_t channels, const uint8_t *__restrict__ bounds, const HoldRuns runs)
+{
+    const uint64_t px = first_pixel + (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x;
+    if (px >= n) return;
+    const uint32_t f0 = runs.first[blockIdx.y], f1 = f0 + runs.len[blockIdx.y];
+    uint8_t *const p = frames + px * channels * sizeof(SAMPLE);
+    uint32_t held[4] = {0, 0, 0, 0}, e[4] = {0, 0, 0, 0};
+    {
+        const SAMPLE *q = reinterpret_cast<const SAMPLE *>(p + (uint64_t)f0 * frame_stride);
+        const SAMPLE *b = reinterpret_cast<const SAMPLE *>(bounds + px * channels * sizeof(SAMPLE));
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c)
+            if (c < channels) { held[c] = q[c]; e[c] = b[c]; }
+    }
+    for (uint32_t f = f0 + 1; f < f1; ++f) {
+        SAMPLE *q = reinterpret_cast<SAMPLE *>(p + (uint64_t)f * frame_stride);
+        uint32_t cur[4] = {0, 0, 0, 0};
+        bool upd = false;
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c)
+            if (c < channels) {
+                cur[c] = q[c];
+                upd |= (cur[c] > held[c] ? cur[c] - held[c] : held[c] - cur[c]) > e[c];
+            }
 #pragma unroll
         for (uint32_t c = 0; c < 4; ++c) {
             held[c] = upd ? cur[c] : held[c];

@@ -164,6 +164,87 @@ __global__ __launch_bounds__(WG_THREADS) void k_temporal_lookahead(uint8_t *__re
         if (start[k] != f0) store_value(k, v);
 }
 
+// Sweep 1 with a bound per sample: e = E[p][c], read from `bounds` -- one dense frame of bounds in the frames' own layout and sample
+// type, a multiple of 8 like the frames.  The lane loads its tile ONCE per run and keeps it as planes (NP more registers), so the
+// windows' saturating add and subtract take a plane of bounds where k_temporal_lookahead repeats one dword.  Everything else -- the
+// stabbing, the clamp, the bitmap, and sweep 2, which never sees a bound -- is that kernel's.  (A sibling and not a template flag, for
+// the reason given at k_hold_map.)
+template <typename SAMPLE, int C>
+__global__ __launch_bounds__(WG_THREADS) void k_lookahead_map(uint8_t *__restrict__ frames, uint64_t frame_stride, uint64_t lanes,
+                                                              const uint8_t *__restrict__ bounds, uint8_t *__restrict__ bits,
+                                                              uint64_t bits_stride, const HoldRuns runs)
+{
+    using G = LaGeom<SAMPLE, C>;
+    constexpr int DW = G::DW, NP = G::NP, K = (int)LA_LANE_PIXELS;
+    const uint64_t lane = (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x;
+    if (lane >= lanes) return;
+    const uint32_t f0 = runs.first[blockIdx.y], f1 = f0 + runs.len[blockIdx.y];
+    if (f1 - f0 < 2) return;
+    uint8_t *const p = frames + lane * (uint64_t)(K * G::PB);
+    uint32_t e[NP], lo[NP], hi[NP], prev[NP], start[K];
+    {
+        uint32_t d[DW];
+        G::load(bounds + lane * (uint64_t)(K * G::PB), d);
+        G::to_planes(d, e);
+        G::load(p + (uint64_t)f0 * frame_stride, d);
+        G::to_planes(d, prev);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) lo[i] = hi[i] = prev[i];
+#pragma unroll
+        for (int k = 0; k < K; ++k) start[k] = f0;
+    }
+    auto store_value = [&](int k, const uint32_t *v) {
+        SAMPLE *const q = reinterpret_cast<SAMPLE *>(p + (uint64_t)start[k] * frame_stride);
+#pragma unroll
+        for (int s = k * C; s < (k + 1) * C; ++s) q[s] = (SAMPLE)(v[G::plane(s)] >> (16 * G::half(s)));
+    };
+    uint32_t nxt[DW];
+    G::load(p + (uint64_t)(f0 + 1) * frame_stride, nxt);
+    for (uint32_t f = f0 + 1; f < f1; ++f) {
+        uint32_t x[NP], xl[NP], xh[NP], bad[NP], v[NP];
+        G::to_planes(nxt, x);
+        if (f + 1 < f1) G::load(p + (uint64_t)(f + 1) * frame_stride, nxt);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            xl[i] = la_subs(x[i], e[i]);
+            xh[i] = la_min(la_adds(x[i], e[i]), G::TOP2);
+            v[i] = la_min(la_max(prev[i], lo[i]), hi[i]);
+            lo[i] = la_max(lo[i], xl[i]);
+            hi[i] = la_min(hi[i], xh[i]);
+            bad[i] = la_subs(lo[i], hi[i]);
+        }
+        uint32_t opened = 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+                if (G::mask(k, i)) any |= bad[i] & G::mask(k, i);
+            if (any) {
+                if (start[k] != f0) store_value(k, v);
+                opened |= 1u << k;
+            }
+            const uint32_t upd = any ? 0xFFFFFFFFu : 0u;
+            start[k] = any ? f : start[k];
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+                if (G::mask(k, i)) {
+                    const uint32_t m = upd & G::mask(k, i);
+                    prev[i] = (v[i] & m) | (prev[i] & ~m);
+                    lo[i] = (xl[i] & m) | (lo[i] & ~m);
+                    hi[i] = (xh[i] & m) | (hi[i] & ~m);
+                }
+        }
+        bits[(uint64_t)f * bits_stride + lane] = (uint8_t)opened;
+    }
+    uint32_t v[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) v[i] = la_min(la_max(prev[i], lo[i]), hi[i]);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (start[k] != f0) store_value(k, v);
+}
+
 // Sweep 2, the same lanes: y = the run's first frame; a frame's pixels with their start bit set are the values sweep 1 left there and
 // become y, the others take y, and the 8-byte vectors that change are written.  A lane whose byte of start bits is zero -- most lanes of
 // most frames once the masks are sparse -- does not read the frame at all: it stores y over it (on footage with sensor noise the frame
@@ -258,6 +339,63 @@ __global__ __launch_bounds__(WG_THREADS) void k_temporal_lookahead_px(uint8_t *_
                 const int32_t x = q[c];
                 xl[c] = max(0, x - e);
                 xh[c] = min(M, x + e);
+                empty |= max(lo[c], xl[c]) > min(hi[c], xh[c]);
+            }
+        if (empty) {
+            close(f);
+            start = f;
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) {
+            lo[c] = empty ? xl[c] : max(lo[c], xl[c]);
+            hi[c] = empty ? xh[c] : min(hi[c], xh[c]);
+        }
+    }
+    close(f1);
+}
+
+// k_temporal_lookahead_px with a bound per sample: the pixel's bounds are read sample by sample from `bounds`, once per run, so any
+// sample-aligned bound frame will do.
+template <typename SAMPLE>
+__global__ __launch_bounds__(WG_THREADS) void k_lookahead_map_px(uint8_t *__restrict__ frames, uint64_t frame_stride, uint64_t first_pixel,
+                                                                 uint64_t n, uint32_t channels, const uint8_t *__restrict__ bounds,
+                                                                 const HoldRuns runs)
+{
+    const uint64_t px = first_pixel + (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x;
+    if (px >= n) return;
+    const uint32_t f0 = runs.first[blockIdx.y], f1 = f0 + runs.len[blockIdx.y];
+    if (f1 - f0 < 2) return;
+    constexpr int32_t M = sizeof(SAMPLE) == 2 ? 0xFFFF : 0xFF;
+    uint8_t *const p = frames + px * channels * sizeof(SAMPLE);
+    int32_t e[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0}, prev[4] = {0, 0, 0, 0};
+    {
+        const SAMPLE *q = reinterpret_cast<const SAMPLE *>(p + (uint64_t)f0 * frame_stride);
+        const SAMPLE *b = reinterpret_cast<const SAMPLE *>(bounds + px * channels * sizeof(SAMPLE));
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c)
+            if (c < channels) { lo[c] = hi[c] = prev[c] = q[c]; e[c] = b[c]; }
+    }
+    uint32_t start = f0 + 1;
+    auto close = [&](uint32_t end) {
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) prev[c] = min(max(prev[c], lo[c]), hi[c]);
+        for (uint32_t f = start; f < end; ++f) {
+            SAMPLE *q = reinterpret_cast<SAMPLE *>(p + (uint64_t)f * frame_stride);
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c)
+                if (c < channels) q[c] = (SAMPLE)prev[c];
+        }
+    };
+    for (uint32_t f = f0 + 1; f < f1; ++f) {
+        const SAMPLE *q = reinterpret_cast<const SAMPLE *>(p + (uint64_t)f * frame_stride);
+        int32_t xl[4] = {0, 0, 0, 0}, xh[4] = {0, 0, 0, 0};
+        bool empty = false;
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c)
+            if (c < channels) {
+                const int32_t x = q[c];
+                xl[c] = max(0, x - e[c]);
+                xh[c] = min(M, x + e[c]);
                 empty |= max(lo[c], xl[c]) > min(hi[c], xh[c]);
             }
         if (empty) {

@@ -62,7 +62,7 @@ class GopCoder:
     def __init__(self, ctx, width, height, nframes, channels=3, sample_bytes=1, seeds=P.SEEDS_VIDEO,
                  allocator=None, threshold=0.0, out_allocator=None, frames_block=None, adaptive=None,
                  planar_luma=False, keep_interleaved=True, resident_gops=1, luma_block=None, run_starts=None, mask_channels=1,
-                 max_error=0, hold_mode="first"):
+                 max_error=0, hold_mode="first", error_bounds=None, keep_originals=False):
         """allocator: device memory source (default: library-owned); out_allocator: separate source for
         the output record (filters, witnesses, stats); frames_block: share another coder's frame buffer.
         threshold=None with adaptive=(noise_tolerance, min_thr, max_thr): per-frame noise-adaptive
@@ -89,6 +89,12 @@ class GopCoder:
         bound, the same exact run firsts, never more updates per pixel.  It is NOT idempotent, so the coder runs it ONCE PER load_frames():
         a second encode() of the same resident GOP skips the stage -- the block already is its held sequence -- and returns the same rows.
         (A block shared through frames_block, or filled behind the coder's back, is the caller's to keep track of: mark_loaded().)
+        error_bounds: None (default), or a BOUND FRAME (container.bounds_frame: an array of exactly a frame's shape and dtype) -- the
+        near-lossless stage with a bound per sample in place of max_error (rbf_temporal_hold_runs_map / rbf_temporal_lookahead_runs_map):
+        every decoded sample is within ITS entry of the original, a pixel whose entries are 0 is exact.  The frame is uploaded once per
+        coder and serves every block.  Needs what max_error > 0 needs, and not max_error > 0 itself; hold_mode applies as above.
+        keep_originals: True = load_frames() also keeps a device copy of the block as it was uploaded (rbf_memcpy_d2d, before any hold),
+        which is what error_stats() compares the coded block with.
         """
         from .engine import threshold_floor
         self.mask_channels = int(mask_channels)
@@ -104,22 +110,31 @@ class GopCoder:
         if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
             raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
         self.max_error = int(max_error)
-        if self.max_error:
-            if self.max_error >> (8 * sample_bytes):
-                raise ValueError("max_error %d does not fit a %d-bit sample" % (self.max_error, 8 * sample_bytes))
+        if self.max_error >> (8 * sample_bytes):
+            raise ValueError("max_error %d does not fit a %d-bit sample" % (self.max_error, 8 * sample_bytes))
+        self.error_bounds = None
+        if error_bounds is not None:
+            if self.max_error:
+                raise ValueError("error_bounds and max_error > 0 are two ways to say the bound: give one")
+            want = ((height, width) if channels == 1 else (height, width, channels)), np.dtype(np.uint8 if sample_bytes == 1 else np.uint16)
+            if not isinstance(error_bounds, np.ndarray) or (error_bounds.shape, error_bounds.dtype) != want:
+                raise ValueError("error_bounds must be a bound frame (container.bounds_frame) of shape %r and dtype %s" % want)
+            self.error_bounds = np.ascontiguousarray(error_bounds)
+        near = "error_bounds" if self.error_bounds is not None else "max_error > 0" if self.max_error else None
+        if near:
             if self.mask_channels != channels:
-                raise ValueError("max_error > 0 holds every sample of a pixel: the mask has to see them all (mask_channels == channels = %d, "
-                                 "got %d)" % (channels, self.mask_channels))
+                raise ValueError("%s holds every sample of a pixel: the mask has to see them all (mask_channels == channels = %d, "
+                                 "got %d)" % (near, channels, self.mask_channels))
             if planar_luma:
-                raise ValueError("max_error > 0 holds the interleaved frames: not with planar_luma")
+                raise ValueError("%s holds the interleaved frames: not with planar_luma" % near)
             if threshold is None or adaptive is not None:
-                raise ValueError("max_error > 0 codes the held frames exactly: no adaptive thresholds")
+                raise ValueError("%s codes the held frames exactly: no adaptive thresholds" % near)
             if not np.ndim(threshold) == 0 or float(threshold) != 0.0:
-                raise ValueError("max_error > 0 codes the held frames exactly: threshold must be 0, got %r" % (threshold,))
+                raise ValueError("%s codes the held frames exactly: threshold must be 0, got %r" % (near, threshold))
         if hold_mode not in ("first", "lookahead"):
             raise ValueError("hold_mode must be 'first' or 'lookahead', got %r" % (hold_mode,))
-        if hold_mode == "lookahead" and not self.max_error:
-            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0")
+        if hold_mode == "lookahead" and not near:
+            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0 or error_bounds")
         self.hold_mode = hold_mode
         self._held = set()                            # look-ahead: the resident GOPs that already are their held sequence
         self.ctx, self.W, self.H, self.F, self.C, self.sb = ctx, width, height, nframes, channels, sample_bytes
@@ -159,6 +174,14 @@ class GopCoder:
         self.stats = oalloc(8 * nat.STATS_PER_FRAME * self.pairs)
         self.params, self.k = (nat.FilterParams * self.pairs)(), (ctypes.c_double * self.pairs)()
         self.record = None
+        self.bounds = None                            # the bound frame on the device
+        if self.error_bounds is not None:
+            self.bounds = alloc(self.frame_bytes)
+            nat.check(nat.lib().rbf_memcpy_h2d(ctx.handle, self.bounds.ptr, self.error_bounds.ctypes.data, self.frame_bytes))
+        self.keep_originals = bool(keep_originals)
+        if self.keep_originals and self.frames is None:
+            raise ValueError("keep_originals copies the interleaved frames (keep_interleaved=True)")
+        self.originals = alloc(self.frame_bytes * nframes * self.resident_gops) if self.keep_originals else None
         if self.adaptive is not None:
             self.moments = alloc(16 * self.pairs)
             self.noise_plane = None                       # allocated on the first exact fallback
@@ -213,6 +236,8 @@ class GopCoder:
         if self.frames is not None:
             dst = self.frames.ptr + gop * self.frame_bytes * self.F
             nat.check(nat.lib().rbf_memcpy_h2d(self.ctx.handle, dst, frames.ctypes.data, frames.nbytes))
+            if self.keep_originals:                   # before any hold rewrites the block
+                nat.check(nat.lib().rbf_memcpy_d2d(self.ctx.handle, self.originals.ptr + gop * self.frame_bytes * self.F, dst, frames.nbytes))
             if self.planar_luma:
                 nat.check(nat.lib().rbf_extract_luma_batch(self.ctx.handle, dst, self.frame_bytes, self.F, self.W, self.H, self.W * self.C * self.sb,
                                                            self.C * self.sb, self.sb, self.luma.ptr + gop * self.luma_bytes * self.F))
@@ -273,14 +298,18 @@ class GopCoder:
             src, fstride, pitch, pstride = self.luma.ptr + gop * self.luma_bytes * self.F, self.luma_bytes, self.W * self.sb, self.sb
         else:
             src, fstride, pitch, pstride = self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.W * self.C * self.sb, self.C * self.sb
-        if self.max_error and self.hold_mode == "lookahead":
+        geometry = (self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb)
+        if (self.max_error or self.bounds is not None) and self.hold_mode == "lookahead":
             if gop not in self._held:                 # not idempotent: once per load_frames(); after that the block IS its held sequence
-                nat.check(nat.lib().rbf_temporal_lookahead_runs(self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb,
-                                                                self.max_error, self.run_starts))
+                if self.bounds is not None:
+                    nat.check(nat.lib().rbf_temporal_lookahead_runs_map(*geometry, self.bounds.ptr, self.run_starts))
+                else:
+                    nat.check(nat.lib().rbf_temporal_lookahead_runs(*geometry, self.max_error, self.run_starts))
                 self._held.add(gop)
-        elif self.max_error:                          # near-lossless: the block becomes its held sequence, which is then coded exactly
-            nat.check(nat.lib().rbf_temporal_hold_runs(self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb, self.max_error,
-                                                       self.run_starts))
+        elif self.bounds is not None:                 # near-lossless: the block becomes its held sequence, which is then coded exactly
+            nat.check(nat.lib().rbf_temporal_hold_runs_map(*geometry, self.bounds.ptr, self.run_starts))
+        elif self.max_error:
+            nat.check(nat.lib().rbf_temporal_hold_runs(*geometry, self.max_error, self.run_starts))
         nat.check(nat.lib().rbf_encode_runs_begin_ex(
             self.ctx.handle, src, fstride, self.F, self.W, self.H,
             pitch, pstride, self.sb, self.thr, self.thr_tab, self.run_starts, ctypes.byref(self.seeds),
@@ -364,6 +393,20 @@ class GopCoder:
                                           self.H, self.C, self.sb, int(tolerance), self._cut_stats.ptr))
         self.ctx.sync()
         return self._cut_stats.numpy(self.ctx, 24 * self.pairs)[:24 * self.pairs].view(np.uint64).reshape(self.pairs, 3).copy()
+
+    def error_stats(self):
+        """What the resident block of the GOP encode() last coded differs from its originals by (keep_originals=True; rbf_error_stats,
+        include/rbf.h): a structured array (_native.ERROR_ROW) of F rows -- sse, differing, over_bound, max_abs per frame, over_bound
+        against the coder's bound frame or its max_error.  One read of both blocks, no decode: a decoder rebuilds the resident block
+        exactly, so this is the decoded clip's quality.  Valid after encode(); blocks until the rows are on the host."""
+        if self.originals is None:
+            raise ValueError("error_stats needs the uploaded frames: GopCoder(keep_originals=True)")
+        off = getattr(self, "gop", 0) * self.frame_bytes * self.F
+        rows = np.zeros(self.F, dtype=nat.ERROR_ROW)
+        nat.check(nat.lib().rbf_error_stats(self.ctx.handle, self.originals.ptr + off, self.frame_bytes, self.frames.ptr + off, self.frame_bytes,
+                                            self.F, self.W, self.H, self.C, self.sb, None if self.bounds is None else self.bounds.ptr,
+                                            self.max_error, rows.ctypes.data))
+        return rows
 
     def frame_digests(self):
         """FD1 of the F resident frames of the GOP encode() last coded (integrity.py): ONE rbf_frame_digest_batch over the block -- bytes the

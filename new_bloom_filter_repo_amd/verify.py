@@ -3,6 +3,7 @@ verify_lossless  -- FixedVideoCompressor.verify_lossless (fixed_video_compressor
 verify_bit_exact -- verify_true_lossless.verify_bit_exact (verify_true_lossless.py:338-492),
                     without the OpenCV diagnostic image dumps.
 verify_max_error -- the near-lossless mode's guarantee (ImprovedVideoCompressor(max_error=...)); the reference has no counterpart.
+quality          -- per-frame error statistics and PSNR of a decoded clip, measured on the GPU (rbf_error_stats); no counterpart either.
 verify_container -- a container against its own frame digests (ImprovedVideoCompressor(frame_digests=True)): needs no originals.
 Unlike the reference (which unwraps with `hasattr(x, 'data')` and then crashes on unequal plain
 ndarrays, whose `.data` is a memoryview) both accept plain ndarrays and YUVFrame wrappers."""
@@ -72,7 +73,12 @@ def verify_max_error(original_frames, decoded_frames, max_error, keyframe_interv
     """The near-lossless guarantee: every decoded sample within max_error of the original.  Returns frame_count, max_abs_error (the worst
     sample, exact integer arithmetic), worst_frame (its index, -1 when every frame is exact), within_bound, and -- when keyframe_interval
     is given -- keyframes_exact: every frame t with t % keyframe_interval == 0 equals its original.  A frame-count or shape mismatch is
-    not within any bound: within_bound False with a `reason`."""
+    not within any bound: within_bound False with a `reason`.
+    max_error may also be anything ImprovedVideoCompressor(error_bounds=...) accepts (container.bounds_frame: per-channel bounds, an
+    (H, W) or an (H, W, C) array): within_bound then says that every sample is within ITS bound, over_bound counts those that are not,
+    and the result's max_error is the largest entry of the bound frame."""
+    if not (isinstance(max_error, (int, np.integer)) and not isinstance(max_error, bool)):
+        return _verify_bound_frame(original_frames, decoded_frames, max_error, keyframe_interval)
     out = {"frame_count": len(original_frames), "max_error": int(max_error), "max_abs_error": 0, "worst_frame": -1, "within_bound": False}
     if len(original_frames) != len(decoded_frames):
         out["reason"] = f"Frame count mismatch: {len(original_frames)} vs {len(decoded_frames)}"
@@ -91,6 +97,100 @@ def verify_max_error(original_frames, decoded_frames, max_error, keyframe_interv
     out["within_bound"] = out["max_abs_error"] <= int(max_error)
     if keyframe_interval:
         out["keyframes_exact"] = keys_exact
+    return out
+
+
+def _verify_bound_frame(original_frames, decoded_frames, error_bounds, keyframe_interval):
+    """verify_max_error against a bound per sample."""
+    from .container import bounds_frame
+    bounds_frame(error_bounds)                                   # (refuses what is no bound at all, whatever the frames are)
+    out = {"frame_count": len(original_frames), "max_error": None, "max_abs_error": 0, "worst_frame": -1, "within_bound": False, "over_bound": 0}
+    if len(original_frames) != len(decoded_frames):
+        out["reason"] = f"Frame count mismatch: {len(original_frames)} vs {len(decoded_frames)}"
+        return out
+    keys_exact, E = True, None
+    for i, (o, d) in enumerate(zip(original_frames, decoded_frames)):
+        o, d = _arr(o), _arr(d)
+        if o.shape != d.shape:
+            out["reason"] = f"Shape mismatch in frame {i}: {o.shape} vs {d.shape}"
+            return out
+        if E is None or E.shape != o.shape or E.dtype != o.dtype:
+            E = bounds_frame(error_bounds, o.shape, o.dtype)
+        diff = np.abs(o.astype(np.int64) - d.astype(np.int64))
+        worst = int(diff.max()) if o.size else 0
+        out["over_bound"] += int(np.count_nonzero(diff > E))
+        if worst > out["max_abs_error"]:
+            out["max_abs_error"], out["worst_frame"] = worst, i
+        if keyframe_interval and i % int(keyframe_interval) == 0 and worst:
+            keys_exact = False
+    out["max_error"] = None if E is None else int(E.max())
+    out["within_bound"] = out["over_bound"] == 0
+    if keyframe_interval:
+        out["keyframes_exact"] = keys_exact
+    return out
+
+
+def quality_rows(rows, samples, bits):
+    """The per-frame dicts of a quality report from rbf_error_stats rows (_native.ERROR_ROW; a frame of `samples` samples of `bits` bits):
+    max_abs_error, mse = sse / samples, psnr = 10 log10((2^bits - 1)^2 / mse) -- inf for an exact frame --, changed_samples, over_bound."""
+    peak2 = float(((1 << bits) - 1) ** 2)
+    out = []
+    for r in rows:
+        sse = int(r["sse"])
+        mse = sse / samples
+        out.append({"max_abs_error": int(r["max_abs"]), "mse": mse, "psnr": float("inf") if sse == 0 else 10.0 * float(np.log10(peak2 / mse)),
+                    "changed_samples": int(r["differing"]), "over_bound": int(r["over_bound"])})
+    return out
+
+
+def quality(original_frames, decoded_frames, error_bounds=None, ctx=None):
+    """What did the decoded clip lose?  One dict per frame (quality_rows) from two lists of frames of one shape and dtype (uint8 / uint16,
+    (H, W) or (H, W, C) with C <= 4), measured on the GPU by rbf_error_stats: both lists are uploaded in chunks of at most 64 frames and
+    compared where they lie.  error_bounds: None -- over_bound counts against 0, so it equals changed_samples; an integer -- against that
+    bound (a max_error=d clip); anything ImprovedVideoCompressor(error_bounds=...) accepts -- against the bound frame.  ctx: the library
+    context to use (default: the process's).  The same numbers as ImprovedVideoCompressor(quality_report=True).last_quality, which needs
+    no decode."""
+    from . import _native as nat
+    from .container import bounds_frame
+    if len(original_frames) != len(decoded_frames):
+        raise ValueError(f"Frame count mismatch: {len(original_frames)} vs {len(decoded_frames)}")
+    if not original_frames:
+        return []
+    first = _arr(original_frames[0])
+    if first.dtype not in (np.uint8, np.uint16) or first.ndim not in (2, 3) or (first.ndim == 3 and not 1 <= first.shape[2] <= 4):
+        raise ValueError("quality compares uint8 / uint16 frames of up to four channels, got %r of %s" % (first.shape, first.dtype))
+    scalar = isinstance(error_bounds, (int, np.integer)) and not isinstance(error_bounds, bool)
+    if scalar and not 0 <= int(error_bounds) <= np.iinfo(first.dtype).max:
+        raise ValueError("error_bounds %r does not fit a %d-bit sample" % (error_bounds, 8 * first.dtype.itemsize))
+    E = None if error_bounds is None or scalar else bounds_frame(error_bounds, first.shape, first.dtype)
+    H, W, C, sb = nat.frame_geometry(first)
+    ctx = ctx or nat.default_context()
+    CHUNK = 64
+    fb = first.nbytes
+    count = min(CHUNK, len(original_frames))
+    a, b, e = ctx.alloc(fb * count), ctx.alloc(fb * count), None
+    out = []
+    try:
+        if E is not None:
+            e = ctx.alloc(fb)
+            nat.check(nat.lib().rbf_memcpy_h2d(ctx.handle, e.ptr, E.ctypes.data, fb))
+        for lo in range(0, len(original_frames), CHUNK):
+            blocks = []
+            for frames in (original_frames, decoded_frames):
+                part = [_arr(f) for f in frames[lo:lo + CHUNK]]
+                if any(f.shape != first.shape or f.dtype != first.dtype for f in part):
+                    raise ValueError("quality needs frames of one shape and dtype (%r of %s)" % (first.shape, first.dtype))
+                blocks.append(np.ascontiguousarray(np.stack(part)))
+            for buf, block in zip((a, b), blocks):
+                nat.check(nat.lib().rbf_memcpy_h2d(ctx.handle, buf.ptr, block.ctypes.data, block.nbytes))
+            rows = np.zeros(len(blocks[0]), dtype=nat.ERROR_ROW)
+            nat.check(nat.lib().rbf_error_stats(ctx.handle, a.ptr, fb, b.ptr, fb, len(rows), W, H, C, sb, None if e is None else e.ptr,
+                                                int(error_bounds) if scalar else 0, rows.ctypes.data))
+            out += quality_rows(rows, H * W * C, 8 * sb)
+    finally:
+        for buf in (a, b, e):
+            if buf is not None:
+                buf.free()
     return out
 
 

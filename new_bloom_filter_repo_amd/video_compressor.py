@@ -75,9 +75,9 @@ class _Lane:
             self.scratch = BufferCache(self.ctx)
         return digests_device(self.ctx, ptr, stride, nframes, frame_bytes, out=self.scratch.get("digests", 8 * nframes))
 
-    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0, hold_mode="first"):
+    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0, hold_mode="first", error_bounds=None, keep_originals=False):
         from .gop import GopCoder
-        key = (W, H, F, C, sb, mask_channels, max_error, hold_mode)
+        key = (W, H, F, C, sb, mask_channels, max_error, hold_mode, id(error_bounds), keep_originals)      # (the compressor keeps its bound frames: ids are stable)
         c = self.coders.get(key)
         if c is None:
             if len(self.coders) >= 2:            # a stream has at most two block sizes (full blocks and its tail)
@@ -85,7 +85,7 @@ class _Lane:
                     old.close()
                 self.coders = {}
             c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels, max_error=max_error,
-                                                hold_mode=hold_mode)
+                                                hold_mode=hold_mode, error_bounds=error_bounds, keep_originals=keep_originals)
         return c
 
     def decode_engine(self):
@@ -151,6 +151,7 @@ class _BlockRecords(list):
     """What _encode_block returns: the per-pair list, with the block's frame digests (uint64 per frame of the block, or None)."""
     digests = None
     cuts = ()                                    # scene_cuts=True: the block indices the cut rule made run starts
+    quality = None                               # quality_report=True: GopCoder.error_stats() of the block, a row per frame
 
 
 def _union_seconds(intervals):
@@ -178,8 +179,8 @@ class ImprovedVideoCompressor:
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
-                 frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False):
-        """Reference signature (improved_video_compressor.py:318-327) plus twelve keyword-only extras:
+                 frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False, error_bounds=None, quality_report=False):
+        """Reference signature (improved_video_compressor.py:318-327) plus fourteen keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -226,7 +227,34 @@ class ImprovedVideoCompressor:
         "lookahead"), and a cut frame is exact like every keyframe.  The keyframe rule itself is unchanged, and decompress_video derives
         its runs from the record types: a fresh default compressor decodes the container.  Needs a resident block to look at: not with
         gop_batching=False, inter_frames=False or keyframe_interval=1; a block the GPU cannot batch is coded as without the keyword.
-        last_scene_cuts lists the cut frames (global indices, ascending) of the last encode_range."""
+        last_scene_cuts lists the cut frames (global indices, ascending) of the last encode_range.
+        error_bounds: None (default), or the near-lossless mode with a bound PER SAMPLE in place of the one number max_error (not both):
+        a sequence of C non-negative integers (one bound per channel: chroma tolerates more than luma), an integer array of shape (H, W)
+        (one bound per pixel: 0 inside a region that must stay exact, any value at a known bad pixel) or one of shape (H, W, C).
+        container.bounds_frame expands it to a bound frame when the first block's shape is known (a shape that does not fit the frames
+        raises before anything is uploaded); the hold kernels read that frame (GopCoder(error_bounds=...)), everything behind them codes
+        the held block exactly, as with max_error: every decoded sample is within ITS bound, keyframes and pixels whose bounds are 0 are
+        exact, a fresh default compressor decodes.  hold_mode applies as above, and what max_error > 0 needs is needed here.  A bound
+        frame whose entries all equal d is coded as max_error=d, byte for byte.  With scene_cuts the cut statistic stays scalar: its
+        tolerance is the SMALLEST entry of the bound frame (doubled for "lookahead") -- a smaller tolerance only counts more pixels as
+        moving, so a frame may become a keyframe that a map-aware statistic would have kept as an inter-frame: that can cost bytes,
+        never correctness.
+        quality_report: False (default) -- nothing is copied or launched.  True -- last_quality holds one dict per frame of the last
+        encode_range, aligned with its records: max_abs_error, mse, psnr (peak 2^B - 1; inf for an exact frame), changed_samples,
+        over_bound (samples further from the original than their bound: 0).  Measured on the GPU from the block each frame was coded in
+        (GopCoder(keep_originals=True).error_stats(): a device copy of the uploaded block against the held one).  The decoder rebuilds
+        the held block exactly -- with frame_digests the container proves it -- so this is the quality of the decoded clip, for one
+        more read of the block and no decode.  A frame that reaches the container from the caller's array (keyframes, exact fallbacks)
+        reports zeros.  Works with max_error=d and with a lossless call too."""
+        self.error_bounds = None
+        if error_bounds is not None:
+            if isinstance(max_error, (int, np.integer)) and not isinstance(max_error, bool) and max_error > 0:
+                raise ValueError("error_bounds and max_error > 0 are two ways to say the bound: give one")
+            container.bounds_frame(error_bounds)     # what can be refused without a frame is refused here
+            self.error_bounds = error_bounds
+        self._bound_frames = {}                  # (frame shape, dtype) -> (the bound frame, its uniform value or None)
+        self.quality_report = bool(quality_report)
+        self.last_quality = None                 # quality_report=True: one dict per frame of the last encode_range
         self.scene_cuts = bool(scene_cuts)
         self.last_scene_cuts = []                # scene_cuts=True: the frames the last encode_range made keyframes because they are cuts
         if self.scene_cuts:
@@ -239,21 +267,22 @@ class ImprovedVideoCompressor:
         self.max_error = int(max_error)
         if hold_mode not in ("first", "lookahead"):
             raise ValueError("hold_mode must be 'first' or 'lookahead', got %r" % (hold_mode,))
-        if hold_mode == "lookahead" and not self.max_error:
-            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0")
+        if hold_mode == "lookahead" and not self.max_error and self.error_bounds is None:
+            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0 or error_bounds")
         self.hold_mode = hold_mode
         self.frame_digests, self.verify_digests = bool(frame_digests), bool(verify_digests)
         self.last_digests = None                 # frame_digests=True: the digests of the last encode_range's frames, aligned with its records
         self.last_integrity = None               # {"frames", "checked", "device", "host"} of the last decompress_video
         self.last_bad_frames = None              # ... and the frames whose digest did not match (decompress_video(on_mismatch="collect"))
         self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
-        if self.max_error:
+        self._near = "error_bounds" if self.error_bounds is not None else "max_error > 0" if self.max_error else None
+        if self._near:
             if mask_channels != "all":
-                raise ValueError("max_error > 0 holds every sample of a pixel: it needs mask_channels='all'")
+                raise ValueError("%s holds every sample of a pixel: it needs mask_channels='all'" % self._near)
             if inter_frames is False or max(1, int(keyframe_interval)) == 1:
-                raise ValueError("max_error > 0 acts on inter-frames: not with inter_frames=False or keyframe_interval=1")
+                raise ValueError("%s acts on inter-frames: not with inter_frames=False or keyframe_interval=1" % self._near)
             if not gop_batching:
-                raise ValueError("max_error > 0 needs gop_batching=True: the frame-by-frame route has no resident run to hold")
+                raise ValueError("%s needs gop_batching=True: the frame-by-frame route has no resident run to hold" % self._near)
         if mask_channels not in ("luma", "all"):
             raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
         if sample_codec not in ("zlib", "rice"):
@@ -397,7 +426,12 @@ class ImprovedVideoCompressor:
             lane = self._get_lanes(1)[0]
         ctx = lane.ctx
         mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
-        coder = lane.coder(W, H, len(seg), C, sb, mc, self.max_error, self.hold_mode)
+        max_error, hold_mode, bounds = self.max_error, self.hold_mode, None
+        if self.error_bounds is not None:
+            bounds, d = self._bound_frame(a)
+            if d is not None:                    # one value everywhere: today's scalar calls, today's bytes
+                max_error, hold_mode, bounds = d, self.hold_mode if d else "first", None
+        coder = lane.coder(W, H, len(seg), C, sb, mc, max_error, hold_mode, bounds, self.quality_report)
         coder.set_run_starts(list(run_starts))
         block = _as_block(data)
         t1 = time.perf_counter()
@@ -405,7 +439,8 @@ class ImprovedVideoCompressor:
         t_up = time.perf_counter()
         cuts = []
         if self.scene_cuts:                      # before any hold rewrites the block; a pixel the hold will keep still is not moving
-            tol = 0 if not self.max_error else self.max_error if self.hold_mode == "first" else 2 * self.max_error
+            tol = max_error if bounds is None else int(bounds.min())          # (the statistic is scalar: the smallest bound)
+            tol = tol if hold_mode == "first" else 2 * tol
             cuts = container.cut_frames(coder.cut_stats(tolerance=min(tol, (1 << (8 * sb)) - 1)), run_starts)
             if cuts:
                 coder.set_run_starts(sorted(set(run_starts) | set(cuts)))
@@ -416,6 +451,7 @@ class ImprovedVideoCompressor:
         t3 = time.perf_counter()
         res = coder.results_packed()
         block_digests = coder.frame_digests() if self.frame_digests else None
+        block_quality = coder.error_stats() if self.quality_report else None
         t4 = time.perf_counter()
         rice = self.sample_codec == "rice"
         if mc == 1:
@@ -434,6 +470,7 @@ class ImprovedVideoCompressor:
         out = _BlockRecords()
         out.digests = block_digests
         out.cuts = tuple(cuts)
+        out.quality = block_quality
         broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
         for f, r in enumerate(res):
             if r.get("skipped"):                 # the pair in front of a keyframe
@@ -441,7 +478,7 @@ class ImprovedVideoCompressor:
                 out.append(None)
                 continue
             if int(uncovered[f]) or broken:      # chroma moved where luma did not: not representable.  With max_error > 0 the rest of the run
-                broken = self.max_error > 0      # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have
+                broken = bool(self._near)        # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have
                 out.append(None)
                 continue
             p = np.uint64(r["ones"]) / n
@@ -481,15 +518,20 @@ class ImprovedVideoCompressor:
         busy = []
         gpu_keys = set()                         # sample_codec="rice": keyframes coded as type-3 records on the lanes
         fixed_keys, blocks = plan_range(first_index, start, stop, I, self.block_frames, inter_frames)
-        if self.max_error and blocks:
+        if self._near and blocks:
+            if self.error_bounds is not None and self.gop_batching:            # a bound frame that does not fit the clip: before any upload
+                a = frame_data(frames[blocks[0][0] - first_index])
+                if a.dtype in (np.uint8, np.uint16) and a.ndim in (2, 3):
+                    self._bound_frame(a)
             off = blocks_off_keyframes(blocks, first_index, I)
             if off:
-                raise ValueError("max_error=%d: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
+                raise ValueError("%s: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
                                  "another block's coder; make block_frames (%d) a multiple of keyframe_interval (%d) and start the range "
-                                 "on a keyframe" % (self.max_error, off[0][0], self.block_frames, I))
+                                 "on a keyframe" % ("max_error=%d" % self.max_error if self.max_error else "error_bounds", off[0][0], self.block_frames, I))
         want = self.frame_digests
         digests = {}                             # frame -> its digest, or the future of the host twin's
         scene_cuts = []
+        quality = {}                             # quality_report: frame -> its row of the block it was coded in
         in_block = {u for lo, end, _ in blocks for u in range(lo, end)} if self.gop_batching else set()
         with ThreadPoolExecutor(self.num_threads) as pool:
             pending = {}
@@ -553,9 +595,11 @@ class ImprovedVideoCompressor:
                     elif inter[j - 1] is not None:
                         pending[u] = (inter_type, inter[j - 1])
                         digest_of(u, bd, j)
+                        if inter.quality is not None:
+                            quality[u] = inter.quality[j]
                         continue
                     key(u)
-                    digest_of(u, None if self.max_error else bd, j)
+                    digest_of(u, None if self._near else bd, j)
             if gpu_keys:
                 t_key = time.perf_counter()
                 for u, rec in self._encode_keys_rice(frames, first_index, sorted(gpu_keys), busy).items():
@@ -569,9 +613,30 @@ class ImprovedVideoCompressor:
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
             self.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (digests[u] for u in range(start, stop))] if want else None
         self.last_scene_cuts = sorted(scene_cuts)
+        self.last_quality = self._quality_dicts(frames, first_index, start, stop, quality) if self.quality_report else None
         _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
         return [records[u] for u in range(start, stop)]
+
+    def _bound_frame(self, a):
+        """(the bound frame of error_bounds for frames like `a`, d if all its entries equal d else None); kept, so that every block of a
+        clip hands its coder the same array."""
+        key = (a.shape, a.dtype.str)
+        if key not in self._bound_frames:
+            E = container.bounds_frame(self.error_bounds, a.shape, a.dtype)
+            self._bound_frames[key] = (E, container.uniform_bound(E))
+        return self._bound_frames[key]
+
+    def _quality_dicts(self, frames, first_index, start, stop, rows):
+        """last_quality: frame u's dict from its block's row (rows[u]); a frame coded from the caller's array is exact -- zeros."""
+        from ._native import ERROR_ROW
+        from .verify import quality_rows
+        out = []
+        for u in range(start, stop):
+            a = frame_data(frames[u - first_index])
+            row = rows.get(u)
+            out += quality_rows([np.zeros((), dtype=ERROR_ROW) if row is None else row], max(1, a.size), 8 * a.dtype.itemsize)
+        return out
 
     def _encode_keys_rice(self, frames, first_index, ts, busy):
         """Type-3 records of the keyframes with global indices `ts`: batches of up to four frames of one shape, ONE rbf_rice_encode_intra
@@ -647,6 +712,9 @@ class ImprovedVideoCompressor:
                    "output_path": output_path, "color_space": input_color_space, "overall_ratio": ratio}
         if self.max_error:
             results["max_error"] = self.max_error
+            results["hold_mode"] = self.hold_mode
+        if self.error_bounds is not None:
+            results["error_bounds"] = True
             results["hold_mode"] = self.hold_mode
         if self.scene_cuts:
             results["scene_cuts"] = list(self.last_scene_cuts)
