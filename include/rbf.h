@@ -580,6 +580,49 @@ int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, co
                     uint32_t nframes, uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                     const void *bounds_dev, uint32_t bound, rbf_error_row *rows_host);
 
+/* ---- pan alignment: the global integer shift of a pair, and the roll that makes a block still ------------------------------------ */
+/* During a camera pan every pixel differs from the pixel at the same position one frame earlier; shifted by the pan it does not.  Let
+ * F_f(p)[c] be sample c of pixel p = (x, y) of frame f, Y_f(p) = F_f(p)[0]; a pair is frame f against frame f-1; R is the range
+ * (1..32) and G = 8 a fixed grid step.  Frames are W x H, with W > 2R and H > 2R.
+ *     grid          the points (x, y) with x in {R, R+G, ...} < W-R and y in {R, R+G, ...} < H-R.  Interior addressing only: no wrap.
+ *     SAD_f(dx,dy)  = sum over the grid of |Y_f(x+dx, y+dy) - Y_{f-1}(x, y)| for |dx|, |dy| <= R: an unsigned 64-bit sum of true
+ *                   absolute differences (16-bit samples 0 and 0x8000 are 32768 apart: no int16 wrap).
+ *     best shift    the candidate that minimises the tuple (SAD, |dx|+|dy|, |dy|, dy, dx) lexicographically: (0, 0) wins every tie.
+ *     moving_f(v)   the number of pixels p of the WHOLE frame for which some sample c of the first `channels` samples has
+ *                   |F_f((p+v) mod (W,H))[c] - F_{f-1}(p)[c]| > tolerance.  Cyclic addressing: exactly what the mask of the rolled
+ *                   block will mark.
+ *     rule          (host, integers, no tunable constant: container.pan_offsets) the pair adopts v_f = best iff
+ *                   moving_f(best) < moving_f(0), else v_f = 0.
+ *     offsets       c_f = 0 at frame 0 and at every run start, else c_f = c_{f-1} + v_f, stored reduced to 0 <= ox < W, 0 <= oy < H.
+ *     stabilised    S_f(p) = F_f((p + c_f) mod (W,H)).  Pair f of the stabilised block differs in exactly moving_f(v_f) pixels.
+ * The model is integer translation: a sub-pixel pan leaves edge residue, and nothing is interpolated.  A cyclic shift is a bijection:
+ * it loses nothing and needs no border side information; the pixels that wrap around are the newly revealed picture content and get
+ * coded as changed pixels.
+ *
+ * rbf_pan_search: frames dense and interleaved as for rbf_cut_stats.  out (HOST, nframes-1 rows) receives for pair f = 1..nframes-1 row
+ * f-1 = {dx, dy of the best shift; sad_zero = SAD(0,0); sad_best; moving_zero = moving(0); moving_best = moving(best)} (moving_best =
+ * moving_zero when best = (0,0)); the row of a pair in front of a run start (run_starts: HOST, nframes bytes, nullable; entry t != 0 =
+ * frame t starts a run) is all zeros.  A workgroup stages a tile of frame f plus a halo of R in LDS and walks the (2R+1)^2 candidates
+ * over it; per-workgroup partial sums are folded and the tie-break applied on the device, where the moving kernel reads the shift: no
+ * atomics, deterministic.  BLOCKS until the rows are on the host.  Not timed: there is no RBF_K_ id for it, as for rbf_cut_stats.
+ * nframes < 2: RBF_OK, nothing is launched.  RBF_EINVAL, with `out` untouched and before anything is launched: range outside 1..32,
+ * width or height <= 2*range, channels outside 1..4, sample_bytes not 1 or 2, tolerance >= 2^B, a null pointer, a base or stride that is
+ * not a multiple of sample_bytes, a stride smaller than a frame.
+ *
+ * rbf_roll_frames: in place on nframes frames of width x height pixels of pixel_bytes (1..8) bytes, no row padding, frame f at
+ * frames_dev + f*frame_stride_bytes:  new_f(x, y) = old_f((x + ox_f) mod W, (y + oy_f) mod H), (ox_f, oy_f) = offsets[2f], offsets[2f+1]
+ * (HOST; any int32, reduced mod W / H).  A frame whose reduced offsets are zero is neither read nor written; bytes between a frame's end
+ * and the next frame's start are never written.  Frames are rolled, a few at a time, into scratch the context keeps and copied back: the
+ * source is never the destination.  Rows of a multiple of 16 bytes move as 16-byte vectors, others byte by byte.  Asynchronous on the
+ * context's stream.  A decoder calls it with the negated offsets.  RBF_EINVAL: pixel_bytes outside 1..8, an empty frame, a null
+ * pointer, a stride smaller than a frame. */
+typedef struct { int32_t dx, dy; uint64_t sad_zero, sad_best, moving_zero, moving_best; } rbf_pan_stat;
+int rbf_pan_search(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                   uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                   uint32_t range, uint32_t tolerance, const uint8_t *run_starts, rbf_pan_stat *out);
+int rbf_roll_frames(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                    uint32_t width, uint32_t height, uint32_t pixel_bytes, const int32_t *offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ class FilterParams(ctypes.Structure):
 
 
 ERROR_ROW = np.dtype([("sse", "<u8"), ("differing", "<u8"), ("over_bound", "<u8"), ("max_abs", "<u4"), ("reserved", "<u4")])     # rbf_error_row
+PAN_ROW = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("sad_zero", "<u8"), ("sad_best", "<u8"), ("moving_zero", "<u8"), ("moving_best", "<u8")])     # rbf_pan_stat
+PAN_MAX_RANGE = 32
 
 
 class Seeds(ctypes.Structure):
@@ -105,6 +107,8 @@ _PROTOS = {
     "rbf_rice_apply_inter": (_int, [_vp, _vp, ctypes.POINTER(_u64), _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
     "rbf_cut_stats": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_error_stats": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "rbf_pan_search": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "rbf_roll_frames": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _i32p]),
     "rbf_frame_digest_batch": (_int, [_vp, _vp, _u64, _u32, _u64, _vp]),
     "rbf_frame_digest_host": (_u64, [_vp, _u64]),
 }

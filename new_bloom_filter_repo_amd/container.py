@@ -8,12 +8,16 @@ every record with a type byte, following the type-byte precedent of VideoFrameCo
   3, 4 = the same two roles with the GPU sample codec in place of zlib-9 (sample_codec.py has their layout),
   5 = the frame digests of all the records in front of it (integrity.py has the layout): optional, only as the LAST record.  It is no
       frame: split_trailer takes it off, and everything else in this module sees the frame records only.
+  6 = the pan table (build_pans has the layout): optional, behind the last frame record and in front of a digest trailer.  It is no frame
+      either: split_tables takes it off.
 """
 import struct
 
 KEY, INTER, KEY_RICE, INTER_RICE = 1, 2, 3, 4
 KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
 DIGESTS = 5
+PANS = 6
+PANS_VERSION = 1
 
 
 def write(records):
@@ -47,10 +51,106 @@ def parse(blob):
     return records
 
 
+def build_pans(entries):
+    """The body of the PANS record: '<B' version = 1 | 3 zero bytes | '<I' count | count x ('<I' record index, '<I' ox, '<I' oy) | '<Q' FD1
+    (rbf_frame_digest_host) of all preceding body bytes.  entries: {record index: (ox, oy)} or [(record index, ox, oy)] -- the cumulative
+    offsets of the inter-frame records whose stabilised frame is not the frame itself ((ox, oy) != (0, 0), 0 <= ox < W, 0 <= oy < H):
+    the record codes S(p) = F((p + (ox, oy)) mod (W, H)), a decoder rolls the rebuilt frame back.  Written ascending by record index."""
+    from .integrity import frame_digest
+    rows = sorted((int(i), int(ox), int(oy)) for i, (ox, oy) in entries.items()) if isinstance(entries, dict) else [tuple(int(v) for v in e) for e in entries]
+    body = struct.pack("<B3xI", PANS_VERSION, len(rows)) + b"".join(struct.pack("<III", *row) for row in rows)
+    return body + struct.pack("<Q", frame_digest(body))
+
+
+def parse_pans(body):
+    """[(record index, ox, oy)] of a PANS record body; a plain ValueError for anything that is not a whole, undamaged version-1 table
+    whose entries ascend by record index and carry a non-zero offset (what the table's own bytes can say: split_tables checks the
+    entries against the container's records)."""
+    from .integrity import frame_digest
+    body = bytes(body)
+    if len(body) < 16:
+        raise ValueError("pan table: its %d bytes are shorter than a table's header and checksum" % len(body))
+    version, z0, z1, z2, count = struct.unpack_from("<BBBBI", body, 0)
+    if version != PANS_VERSION:
+        raise ValueError("pan table version %d is unknown (this reader knows %d)" % (version, PANS_VERSION))
+    if z0 or z1 or z2:
+        raise ValueError("pan table: reserved bytes are not zero")
+    if len(body) != 8 + 12 * count + 8:
+        raise ValueError("pan table of %d bytes does not hold the %d entries it declares" % (len(body), count))
+    (stored,) = struct.unpack_from("<Q", body, len(body) - 8)
+    if stored != frame_digest(body[:-8]):
+        raise ValueError("pan table is damaged: its own checksum does not match")
+    rows = [struct.unpack_from("<III", body, 8 + 12 * j) for j in range(count)]
+    if not rows:
+        raise ValueError("pan table without entries: a container without pans carries no table")
+    for a, b in zip(rows, rows[1:]):
+        if b[0] <= a[0]:
+            raise ValueError("pan table: record index %d after %d, the entries must ascend" % (b[0], a[0]))
+    for i, ox, oy in rows:
+        if ox == 0 and oy == 0:
+            raise ValueError("pan table: record %d has offset (0, 0), which is no entry" % i)
+    return rows
+
+
+def split_tables(records, frame_shape=None):
+    """(frame records, pans, digests) of a container's records: split_trailer, and the PANS record taken off as well.  pans: {record index:
+    (ox, oy)}, empty without a table.  A plain ValueError when the table is there twice, does not stand directly behind the last frame
+    record (in front of a digest trailer, if there is one), is damaged (parse_pans), or names a record that is no inter-frame.
+    frame_shape: (H, W) of the frames when the caller knows it -- an offset outside 0 <= ox < W, 0 <= oy < H is then refused too
+    (check_pans does that for a caller who learns the shape later)."""
+    at = [i for i, (ty, _) in enumerate(records) if ty == PANS]
+    if not at:
+        frames, digests = split_trailer(records)
+        return frames, {}, digests
+    if len(at) > 1:
+        raise ValueError("%d pan tables (records %s): a container has at most one" % (len(at), at))
+    rest = list(records[:at[0]]) + list(records[at[0] + 1:])
+    frames, digests = split_trailer(rest)
+    if at[0] != len(frames):
+        raise ValueError("the pan table is record %d, behind %d frame records: it stands directly behind the last frame record" % (at[0], len(frames)))
+    pans = {}
+    for i, ox, oy in parse_pans(records[at[0]][1]):
+        if i >= len(frames) or frames[i][0] not in INTERS:
+            raise ValueError("pan table: record %d is no inter-frame record" % i)
+        pans[i] = (ox, oy)
+    if frame_shape is not None:
+        check_pans(pans, frame_shape)
+    return frames, pans, digests
+
+
+def check_pans(pans, frame_shape):
+    """ValueError unless every offset of a pan table fits frames of frame_shape = (H, W, ...)."""
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    for i, (ox, oy) in sorted(pans.items()):
+        if not (0 <= ox < W and 0 <= oy < H):
+            raise ValueError("pan table: record %d has offset (%d, %d) outside a frame of %dx%d" % (i, ox, oy, W, H))
+
+
+def pan_offsets(stats, run_starts, W, H):
+    """The pan rule and the accumulation on the rows of a block (GopCoder.align_pans: one row per pair, row j - 1 for frame j of the block,
+    fields dx, dy, moving_zero, moving_best -- include/rbf.h, rbf_pan_search): pair j adopts v_j = (dx, dy) iff moving_best < moving_zero,
+    else v_j = 0 -- integers, no tunable constant; c_0 = 0 and c_j = 0 at every run start, else c_j = c_{j-1} + v_j, reduced to
+    0 <= ox < W, 0 <= oy < H.  Returns (offsets, adopted): offsets[j] = (ox, oy) for every frame j of the block, adopted = [(j, dx, dy)]
+    for the pairs that adopted a shift, ascending."""
+    starts = {int(t) for t in run_starts or ()}
+    offsets, adopted = [(0, 0)], []
+    for j, row in enumerate(stats, start=1):
+        if j in starts:
+            offsets.append((0, 0))
+            continue
+        dx, dy = int(row["dx"]), int(row["dy"])
+        ox, oy = offsets[-1]
+        if (dx or dy) and int(row["moving_best"]) < int(row["moving_zero"]):
+            adopted.append((j, dx, dy))
+            ox, oy = (ox + dx) % int(W), (oy + dy) % int(H)
+        offsets.append((ox, oy))
+    return offsets, adopted
+
+
 def split_trailer(records):
     """(frame records, digests): the digests of a container's DIGESTS record, one per frame record, or None when it has none.  A plain
     ValueError -- never an integrity error, which speaks of frames -- when the trailer is not the last record, is there twice, does not
-    cover exactly the frame records in front of it, or is damaged (integrity.parse_trailer)."""
+    cover exactly the frame records in front of it, or is damaged (integrity.parse_trailer).  (A container with a pan table: split_tables.)"""
     at = [i for i, (ty, _) in enumerate(records) if ty == DIGESTS]
     if not at:
         return list(records), None

@@ -20,9 +20,11 @@
 #include "rbf_kernels_digest.h"
 #include "rbf_kernels_cut.h"
 #include "rbf_kernels_error.h"
+#include "rbf_kernels_pan.h"
 #include "rbf_rice_host.h"
 
 #include <cmath>
+#include <cstring>
 
 // ------------------------------------------------------------------------------------------
 // A1: the mask stage
@@ -1713,6 +1715,120 @@ int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, co
     HIP_TRY(hipMemcpyAsync(rows_host, ctx->err_rows.p, (size_t)nframes * sizeof(ErrorRow), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RBF_OK;
+}
+
+// ---- pan alignment: the global integer shift of every pair and the roll that makes the block still (rbf_kernels_pan.h)
+int rbf_pan_search(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                   uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                   uint32_t range, uint32_t tolerance, const uint8_t *run_starts, rbf_pan_stat *out)
+{
+    static_assert(sizeof(PanRow) == sizeof(rbf_pan_stat) && sizeof(rbf_pan_stat) == 40, "the kernels write the ABI's rows");
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    if (int r = check_layout(l, nframes, rules)) return r;
+    if (range < 1 || range > (uint32_t)PAN_MAX_RANGE) return fail(RBF_EINVAL, "range must be 1..%d, got %u", PAN_MAX_RANGE, range);
+    if (width <= 2 * range || height <= 2 * range)
+        return fail(RBF_EINVAL, "a frame of %ux%u has no grid point for range %u: width and height must exceed 2 * range", width, height, range);
+    if (tolerance >> (8 * sample_bytes)) return fail(RBF_EINVAL, "tolerance %u does not fit a %u-bit sample", tolerance, 8 * sample_bytes);
+    if (nframes < 2) return RBF_OK;                               // no pair
+    if (!frames_dev || !out) return fail(RBF_EINVAL, "null pointer");
+    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    const uint32_t pairs = nframes - 1;
+    if (pairs > 65535) return fail(RBF_ERANGE, "at most 65536 frames per call, got %u", nframes);
+    const uint32_t ngx = (width - 2 * range + PAN_GRID - 1) / PAN_GRID, ngy = (height - 2 * range + PAN_GRID - 1) / PAN_GRID;
+    const uint32_t tiles_x = (ngx + PAN_TX - 1) / PAN_TX, tiles_y = (ngy + PAN_TY - 1) / PAN_TY;
+    const uint64_t tiles = (uint64_t)tiles_x * tiles_y, nd = 2 * range + 1;
+    const uint64_t bx = (n + WG_THREADS - 1) / WG_THREADS, rows = bx * WG_WAVES;
+    if (tiles > 0x7FFFFFFFull || bx > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    if (int r = ctx->pan_partials.reserve((size_t)pairs * tiles * nd * nd * 4)) return r;
+    if (int r = ctx->pan_moving.reserve((size_t)pairs * rows * PAN_COUNTS * 4)) return r;
+    if (int r = ctx->pan_rows.reserve((size_t)pairs * sizeof(PanRow))) return r;
+    if (int r = ctx->pan_runs.reserve((size_t)nframes)) return r;
+    std::vector<uint8_t> starts;
+    try { starts.assign(nframes, 0); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    if (run_starts)
+        for (uint32_t t = 1; t < nframes; ++t) starts[t] = run_starts[t] ? 1 : 0;
+    HIP_TRY(hipMemcpyAsync(ctx->pan_runs.p, starts.data(), nframes, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t *const frames = (const uint8_t *)frames_dev;
+    PanRow *const prow = (PanRow *)ctx->pan_rows.p;
+    const uint32_t lds = pan_sad_lds_bytes(range, sample_bytes);
+    {
+        const dim3 grid((uint32_t)tiles, pairs), block(WG_THREADS);
+#define RBF_PAN_SAD(S, RM) hipLaunchKernelGGL((k_pan_sad<S, RM>), grid, block, lds, ctx->stream, frames, frame_stride_bytes, width, height, channels, range, ngx, ngy, tiles_x, ctx->pan_runs.p, ctx->pan_partials.p)
+        by_sample_width(sample_bytes, [&](auto s) {
+            using S = decltype(s);
+            if (range <= 8) RBF_PAN_SAD(S, 8); else if (range <= 16) RBF_PAN_SAD(S, 16); else RBF_PAN_SAD(S, 32);
+        });
+#undef RBF_PAN_SAD
+    }
+    hipLaunchKernelGGL(k_pan_pick, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, ctx->pan_partials.p, (uint32_t)tiles, range, ctx->pan_runs.p, prow);
+    {
+        const dim3 grid((uint32_t)bx, pairs), block(WG_THREADS);
+#define RBF_PAN_MOV(S, C) hipLaunchKernelGGL((k_pan_moving<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, width, height, tolerance, ctx->pan_runs.p, prow, ctx->pan_moving.p, rows)
+        if (sample_bytes == 1) { if (channels == 1) RBF_PAN_MOV(uint8_t, 1); else if (channels == 2) RBF_PAN_MOV(uint8_t, 2); else if (channels == 3) RBF_PAN_MOV(uint8_t, 3); else RBF_PAN_MOV(uint8_t, 4); }
+        else { if (channels == 1) RBF_PAN_MOV(uint16_t, 1); else if (channels == 2) RBF_PAN_MOV(uint16_t, 2); else if (channels == 3) RBF_PAN_MOV(uint16_t, 3); else RBF_PAN_MOV(uint16_t, 4); }
+#undef RBF_PAN_MOV
+    }
+    hipLaunchKernelGGL(k_pan_moving_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, ctx->pan_moving.p, rows, ctx->pan_runs.p, prow);
+    HIP_TRY(hipGetLastError());
+    if (int r = ctx->pan_host.reserve_rows(pairs)) return r;      // (out is written only by a call that succeeded)
+    HIP_TRY(hipMemcpyAsync(ctx->pan_host.rows.data(), prow, (size_t)pairs * sizeof(PanRow), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(out, ctx->pan_host.rows.data(), (size_t)pairs * sizeof(PanRow));
+    return RBF_OK;
+}
+
+int rbf_roll_frames(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                    uint32_t width, uint32_t height, uint32_t pixel_bytes, const int32_t *offsets)
+{
+    if (int r = set_device(ctx)) return r;
+    if (width == 0 || height == 0) return fail(RBF_EINVAL, "empty frame %ux%u", width, height);
+    if (pixel_bytes < 1 || pixel_bytes > 8) return fail(RBF_EINVAL, "pixel_bytes must be 1..8, got %u", pixel_bytes);
+    const uint64_t row_bytes = (uint64_t)width * pixel_bytes, frame_bytes = row_bytes * height;
+    if (row_bytes > 0x7FFFFFFFull) return fail(RBF_ERANGE, "a row of %llu bytes is too long", (unsigned long long)row_bytes);
+    if (nframes == 0) return RBF_OK;
+    if (!frames_dev || !offsets) return fail(RBF_EINVAL, "null pointer");
+    if (nframes > 1 && frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    const bool vec = !ctx->knobs.force_generic && row_bytes % 16 == 0;
+    const uint64_t per_thread = vec ? 16 : 1, bx = (frame_bytes + per_thread * WG_THREADS - 1) / (per_thread * WG_THREADS);
+    if (bx > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu bytes is too large", (unsigned long long)frame_bytes);
+    uint8_t *const frames = (uint8_t *)frames_dev;
+    RollJobs jobs{};
+    uint32_t cnt = 0;
+    auto flush = [&]() -> int {
+        if (!cnt) return RBF_OK;
+        if (int r = ctx->roll_scratch.reserve((size_t)ROLL_CHUNK * frame_bytes)) return r;
+        const dim3 grid((uint32_t)bx, cnt), block(WG_THREADS);
+        if (vec)
+            hipLaunchKernelGGL(k_roll_frames, grid, block, 0, ctx->stream, frames, frame_stride_bytes, (uint32_t)row_bytes, height, pixel_bytes, jobs, ctx->roll_scratch.p, frame_bytes);
+        else
+            hipLaunchKernelGGL(k_roll_frames_bytes, grid, block, 0, ctx->stream, frames, frame_stride_bytes, (uint32_t)row_bytes, height, pixel_bytes, jobs, ctx->roll_scratch.p, frame_bytes);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t j = 0; j < cnt;) {                          // back into the block: frames that follow each other without a gap in one copy
+            uint32_t e = j + 1;
+            while (e < cnt && jobs.frame[e] == jobs.frame[e - 1] + 1 && frame_stride_bytes == frame_bytes) ++e;
+            HIP_TRY(hipMemcpyAsync(frames + (uint64_t)jobs.frame[j] * frame_stride_bytes, ctx->roll_scratch.p + (uint64_t)j * frame_bytes,
+                                   (size_t)(e - j) * frame_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+            j = e;
+        }
+        cnt = 0;
+        return RBF_OK;
+    };
+    for (uint32_t f = 0; f < nframes; ++f) {
+        const int64_t ox = ((int64_t)offsets[2 * f] % (int64_t)width + width) % width, oy = ((int64_t)offsets[2 * f + 1] % (int64_t)height + height) % height;
+        if (!ox && !oy) continue;                                 // neither read nor written
+        jobs.frame[cnt] = f; jobs.ox[cnt] = (uint32_t)ox; jobs.oy[cnt] = (uint32_t)oy;
+        if (++cnt == ROLL_CHUNK)
+            if (int r = flush()) return r;
+    }
+    return flush();
 }
 
 // ---- integrity: FD1 frame digests (rbf_digest.h, rbf_kernels_digest.h)

@@ -115,6 +115,15 @@ struct rbf_ctx {
     DevBuf<uint32_t> cut_partials;   // scene-cut statistics (rbf_kernels_cut.h): three sums per wave and pair of the call
     DevBuf<uint32_t> err_partials;   // quality report (rbf_kernels_error.h): six words per wave and frame of the call
     DevBuf<void> err_rows;           // ... and the folded rows (rbf_error_row), a frame each, on their way to the host
+    DevBuf<uint32_t> pan_partials;   // pan search (rbf_kernels_pan.h): (2R+1)^2 sums per tile and pair of the call
+    DevBuf<uint32_t> pan_moving;     // ... two counts per wave and pair
+    DevBuf<void> pan_rows;           // ... the folded rows (rbf_pan_stat), a pair each: the pick's shift stays here for the moving kernel
+    DevBuf<uint8_t> pan_runs;        // ... the call's run starts, a byte per frame
+    struct PanHost {                 // ... and the rows on their way to the caller's array
+        std::vector<rbf_pan_stat> rows;
+        int reserve_rows(size_t n) { try { if (rows.size() < n) rows.resize(n); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); } return RBF_OK; }
+    } pan_host;
+    DevBuf<uint8_t> roll_scratch;    // rbf_roll_frames: where a chunk of up to eight frames is rolled to before it is copied back
     struct SharedHashTable *hash_shared = nullptr;               // the pixel-index hash table this context holds a reference to
     uint4 *hash_tab = nullptr;                                    // = hash_shared->table
     // host staging of encode_gop: device-visible pinned block [flag | ones...] the GPU publishes into

@@ -343,7 +343,7 @@ def gather_values(ctx, frame, mask_packed):
     return vals
 
 
-def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt=None):
+def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt=None, before_download=None):
     """The chunked device-side rebuild of a run of inter-frames after `base` that both record types share (apply_chain below, SampleCoder.
     apply_chain).  The run is rebuilt in chunks of at most `chunk_frames` frames and `chunk_bytes` bytes (1080p YUV444: 41 frames; an 8K
     16-bit frame: one at a time -- device block and host block stay bounded whatever the frame size): one upload of the chunk's predecessor
@@ -351,7 +351,11 @@ def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild,
     c0 .. c0+cnt-1 of the run into slots 1 .. cnt, no host round trip in between; the chunk's frames come back in ONE download.
     alloc(name, nbytes): the device blocks.  on_rebuilt(ptr, frame_bytes, count), optional: called after rebuild(...) and before the chunk's
     download with the device address of the chunk's `count` rebuilt frames, frame_bytes apart -- where the frame digests of a container
-    with a trailer are taken (integrity.py), from bytes the scatter has just written.  Returns the list of frames.  They are VIEWS of the
+    with a trailer are taken (integrity.py), from bytes the scatter has just written.  before_download(fb, c0, count), optional: called
+    after that hook, for a caller that changes the chunk's frames on the device before they come back (a panned run is rolled back here:
+    video_compressor._decode_run).  The next chunk still has to see the frame the device REBUILT as its predecessor, not what was
+    downloaded: a hook that returns True has put that frame into slot 0 itself (device to device, before it changed slot `count`), and
+    the next chunk's upload of its predecessor is skipped.  Returns the list of frames.  They are VIEWS of the
     downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
     H, W, _, _ = nat.frame_geometry(base)
     n = H * W
@@ -364,24 +368,26 @@ def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild,
     per = max(1, min(int(chunk_frames), total, int(chunk_bytes) // max(1, fbytes)))
     fb = alloc("chain", (per + 1) * fbytes)                       # slot 0: the predecessor of the chunk's first frame
     mb = alloc("masks", per * stride)
-    prev = base
+    prev, resident = base, False                                  # resident: slot 0 already holds the chunk's predecessor
     for c0 in range(0, total, per):
         cnt = min(per, total - c0)
-        fb.upload(prev, 0)
+        if not resident:
+            fb.upload(prev, 0)
         mb.upload(nat.mask_rows(masks_packed[c0:c0 + cnt], n))
         rebuild(c0, cnt, fb, mb)
         if on_rebuilt is not None:
             on_rebuilt(fb.ptr + fbytes, fbytes, cnt)
+        resident = bool(before_download(fb, c0, cnt)) if before_download is not None else False
         block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
         out += [block[j] for j in range(cnt)]
         prev = block[cnt - 1]
     return out
 
 
-def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None):
+def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None):
     """A8 for a run of inter-frames: frame t = frame t-1 with `values_list[t]` written at mask t's '1' pixels
     (improved_video_compressor.py:849-909), rebuilt ON THE DEVICE in chunks (rebuild_chain): one upload of the chunk's values, then per
-    frame a device-to-device copy of its predecessor and one scatter.  on_rebuilt: rebuild_chain's hook.
+    frame a device-to-device copy of its predecessor and one scatter.  on_rebuilt, before_download: rebuild_chain's hooks.
     Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
     base = np.ascontiguousarray(base)
     H, W, C, sb = nat.frame_geometry(base)
@@ -414,7 +420,7 @@ def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_byt
             dst = fb.ptr + (j + 1) * fbytes
             nat.check(L.rbf_memcpy_d2d(ctx.handle, dst, fb.ptr + j * fbytes, fbytes))
             nat.check(L.rbf_scatter_values(ctx.handle, dst, W, H, W * C * sb, C * sb, sb, C, mb.ptr + j * stride, vb.ptr + offs[j]))
-    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt)
+    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download)
     for b in bufs:
         b.free()
     return out

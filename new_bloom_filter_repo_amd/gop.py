@@ -394,6 +394,50 @@ class GopCoder:
         self.ctx.sync()
         return self._cut_stats.numpy(self.ctx, 24 * self.pairs)[:24 * self.pairs].view(np.uint64).reshape(self.pairs, 3).copy()
 
+    def pan_search(self, pan_range, tolerance=0, gop=0):
+        """The pan statistics of resident GOP `gop` (rbf_pan_search, include/rbf.h): a structured array (_native.PAN_ROW) of `pairs` rows
+        -- the best integer shift of frame f + 1 against frame f within +-pan_range pixels, its SAD and the SAD of no shift on the luma
+        grid, and how many pixels of the whole frame move with and without it (tolerance as in cut_stats).  Read-only on the block AS IT
+        IS NOW, with the coder's current run starts (the row in front of one is zeros); blocks until the rows are on the host."""
+        if self.planar_luma or self.frames is None:
+            raise ValueError("the pan search reads the interleaved frames: not with planar_luma")
+        assert 0 <= gop < self.resident_gops
+        rows = np.zeros(self.pairs, dtype=nat.PAN_ROW)
+        if self.pairs:
+            nat.check(nat.lib().rbf_pan_search(self.ctx.handle, self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+                                               self.H, self.C, self.sb, int(pan_range), int(tolerance), self.run_starts, rows.ctypes.data))
+        return rows
+
+    def roll_frames(self, offsets, gop=0):
+        """Roll the frames of resident GOP `gop` in place (rbf_roll_frames): frame j becomes new(x, y) = old((x + ox_j) mod W, (y + oy_j)
+        mod H) with offsets[j] = (ox_j, oy_j); a frame with a zero offset is not touched.  With keep_originals the originals copy is rolled
+        by the same offsets, so that error_stats() still compares like with like."""
+        if self.planar_luma or self.frames is None:
+            raise ValueError("the roll moves the interleaved frames: not with planar_luma")
+        assert len(offsets) == self.F and 0 <= gop < self.resident_gops
+        if not any(int(ox) % self.W or int(oy) % self.H for ox, oy in offsets):
+            return
+        flat = (ctypes.c_int32 * (2 * self.F))(*[int(v) for o in offsets for v in o])
+        for block in (self.frames, self.originals):
+            if block is not None:
+                nat.check(nat.lib().rbf_roll_frames(self.ctx.handle, block.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+                                                    self.H, self.C * self.sb, flat))
+        self.mark_loaded(gop)                         # the block holds new input: a look-ahead hold runs after the roll, not before
+
+    def align_pans(self, pan_range, tolerance=0, gop=0):
+        """Make resident GOP `gop` still: search every pair's shift (pan_search), apply the rule and accumulate (container.pan_offsets: a
+        pair adopts its best shift iff fewer pixels move with it; the offsets add up along a run and start at 0 at every run start) and
+        roll every frame by its cumulative offset in place (roll_frames) -- frame j then holds S_j(p) = F_j((p + c_j) mod (W, H)), and pair
+        j of the block differs in exactly moving_best (or moving_zero) pixels.  Call it directly after load_frames(), before cut_stats()
+        and encode().  Returns (offsets, rows, adopted): the F cumulative offsets (ox, oy), the rows of pan_search, and pan_offsets'
+        [(j, dx, dy)] of the pairs that adopted a shift.  Not for a planar_luma coder."""
+        from .container import pan_offsets
+        rows = self.pan_search(pan_range, tolerance, gop)
+        starts = [t for t in range(1, self.F) if self.run_starts is not None and self.run_starts[t]]
+        offsets, adopted = pan_offsets(rows, starts, self.W, self.H)
+        self.roll_frames(offsets, gop)
+        return offsets, rows, adopted
+
     def error_stats(self):
         """What the resident block of the GOP encode() last coded differs from its originals by (keep_originals=True; rbf_error_stats,
         include/rbf.h): a structured array (_native.ERROR_ROW) of F rows -- sse, differing, over_bound, max_abs per frame, over_bound

@@ -171,10 +171,10 @@ class SampleCoder:
         out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
         return out.reshape((height, width) if channels == 0 else (height, width, C))
 
-    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None):
+    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None):
         """engine.apply_chain for type-4 records: frame t = frame t-1 plus the residuals of stream t at mask t's '1' pixels, rebuilt on the
-        device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  on_rebuilt:
-        rebuild_chain's hook.  Returns the frames as views of the downloaded chunk blocks."""
+        device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  on_rebuilt,
+        before_download: rebuild_chain's hooks.  Returns the frames as views of the downloaded chunk blocks."""
         base = np.ascontiguousarray(base)
         H, W, C, sb = nat.frame_geometry(base)
         stride = nat.packed_stride(H * W)
@@ -184,4 +184,4 @@ class SampleCoder:
             blob = np.frombuffer(b"".join(part), dtype=np.uint8)
             sizes = (ctypes.c_uint64 * cnt)(*[len(s) for s in part])
             nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, sb, mb.ptr, stride, fb.ptr))
-        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt)
+        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download)

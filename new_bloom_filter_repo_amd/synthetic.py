@@ -86,6 +86,39 @@ def _rgb_to_yuv444(rgb, bits):
     return np.clip(np.rint(np.stack([y, u, v], axis=-1)), 0, top)
 
 
+def make_panning_gop(seed, width, height, nframes, velocities, moving=0.01, dtype=np.uint8, color_space="YUV", sensor_noise=0,
+                     return_shifts=False):
+    """nframes (H, W, 3) frames of a panning camera: a width x height window that moves over a larger make_camera_gop canvas (same seed and
+    keywords: the scene changes under the window the way it does there).  velocities: one (vx, vy) -- the window moves that many pixels
+    per frame -- or a sequence of nframes - 1 of them, one per pair ((0, 0) entries make a static stretch).  The window starts in the
+    canvas's centre; the canvas has a margin of max(largest |v|, 15 % of the frame) on every side, so it stays within about 1.3x of the
+    frame in each direction, and the path goes back and forth: a component that would leave the margin changes its sign from that pair
+    on.  The picture content moves against the window, so the shift that aligns frame f with frame f-1 in the sense of rbf_pan_search
+    (include/rbf.h) is (-vx, -vy) of the pair's actual velocity; return_shifts=True returns (frames, shifts) with those shifts,
+    shifts[f-1] for frame f."""
+    vel = np.asarray(velocities, dtype=np.int64)
+    if vel.ndim == 1:
+        vel = np.tile(vel, (max(0, nframes - 1), 1))
+    if vel.shape != (max(0, nframes - 1), 2):
+        raise ValueError("velocities must be one (vx, vy) or nframes - 1 = %d of them, got shape %r" % (nframes - 1, vel.shape))
+    top = int(np.abs(vel).max()) if vel.size else 0
+    mx, my = max(top, -(-15 * width // 100)), max(top, -(-15 * height // 100))
+    canvas = make_camera_gop(seed, width + 2 * mx, height + 2 * my, nframes, moving=moving, dtype=dtype, color_space=color_space,
+                             sensor_noise=sensor_noise)
+    px, py, sx, sy = mx, my, 1, 1
+    frames, shifts = [np.ascontiguousarray(canvas[0][py:py + height, px:px + width])], []
+    for f in range(1, nframes):
+        vx, vy = int(vel[f - 1, 0]), int(vel[f - 1, 1])
+        if not 0 <= px + sx * vx <= 2 * mx:
+            sx = -sx
+        if not 0 <= py + sy * vy <= 2 * my:
+            sy = -sy
+        px, py = px + sx * vx, py + sy * vy
+        shifts.append((-sx * vx, -sy * vy))
+        frames.append(np.ascontiguousarray(canvas[f][py:py + height, px:px + width]))
+    return (frames, shifts) if return_shifts else frames
+
+
 def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, color_space="YUV", sensor_noise=0):
     """nframes (H, W, 3) frames that change the way camera footage does, unlike make_gop: a smooth RGB texture of which a Bernoulli(moving)
     set of pixels is perturbed by a few levels per channel in every pair, then converted to YUV444 (BT.601, rounded) -- so in every pair

@@ -26,7 +26,7 @@ import numpy as np
 from . import container
 from . import params as P
 from ._native import frame_geometry
-from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, blocks_off_keyframes, is_keyframe, plan_range
+from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, PANS, blocks_off_keyframes, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
 from .integrity import IntegrityError, build_trailer, digests_device, frame_digest_host
 from .sample_codec import key_format, key_record, parse_key_record, stream_info
@@ -151,6 +151,8 @@ class _BlockRecords(list):
     """What _encode_block returns: the per-pair list, with the block's frame digests (uint64 per frame of the block, or None)."""
     digests = None
     cuts = ()                                    # scene_cuts=True: the block indices the cut rule made run starts
+    pan_offsets = None                           # pan_range > 0: the frames' cumulative offsets (ox, oy) in the block, or None
+    pans = ()                                    # ... and [(block index, dx, dy)] of the pairs that adopted a shift
     quality = None                               # quality_report=True: GopCoder.error_stats() of the block, a row per frame
 
 
@@ -179,8 +181,9 @@ class ImprovedVideoCompressor:
                  max_diff_threshold=30.0, bloom_threshold_modifier=1.0, batch_size=30,
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
-                 frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False, error_bounds=None, quality_report=False):
-        """Reference signature (improved_video_compressor.py:318-327) plus fourteen keyword-only extras:
+                 frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False, error_bounds=None, quality_report=False,
+                 pan_range=0):
+        """Reference signature (improved_video_compressor.py:318-327) plus fifteen keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -245,7 +248,39 @@ class ImprovedVideoCompressor:
         (GopCoder(keep_originals=True).error_stats(): a device copy of the uploaded block against the held one).  The decoder rebuilds
         the held block exactly -- with frame_digests the container proves it -- so this is the quality of the decoded clip, for one
         more read of the block and no decode.  A frame that reaches the container from the caller's array (keyframes, exact fallbacks)
-        reports zeros.  Works with max_error=d and with a lossless call too."""
+        reports zeros.  Works with max_error=d and with a lossless call too.
+        pan_range: 0 (default) -- nothing is launched and the container is today's, byte for byte.  R in 1..32 -- pan alignment: while the
+        camera pans, every pixel differs from the one at its position a frame earlier, the mask is all ones and the Bloom stage never
+        runs.  Right after a block's upload the GPU finds every pair's global integer shift within +-R pixels (GopCoder.align_pans:
+        rbf_pan_search, SAD on a luma grid; include/rbf.h has the definitions), a pair adopts it iff fewer pixels move with it than
+        without (container.pan_offsets: integers, no tunable constant), and every frame is rolled cyclically by its run's cumulative
+        offset (rbf_roll_frames) -- a bijection: nothing is lost, and the pixels that wrap around are the newly revealed content, coded
+        as changed pixels.  Cut statistic, hold, mask stage, Bloom kernels, sample codec and digests then see a still block and are the
+        code they are; the offsets travel in a type-6 record (container.build_pans) that is written only when some pair adopted a
+        shift, so a clip without a pan gets today's bytes.  decompress_video rolls every rebuilt frame back on the device; a fresh
+        default compressor decodes.  The model is integer translation only: a sub-pixel pan leaves edge residue, which a near-lossless
+        hold absorbs in part and a lossless call codes; nothing is interpolated.  Keyframes, scene cuts included, always have offset 0.
+        Needs gop_batching=True, inter-frames, keyframe_interval > 1, mask_channels="all" and blocks that start at keyframes (as
+        max_error > 0 does); not with error_bounds that differ from pixel to pixel (the bound map would no longer sit on the pixels it
+        was drawn for; per-channel bounds are fine).  A block whose frames are not larger than 2R in both directions is coded as
+        without the keyword.  last_pans lists (global frame index, dx, dy) for every pair of the last encode_range that adopted a shift."""
+        if isinstance(pan_range, bool) or not isinstance(pan_range, (int, np.integer)) or not 0 <= pan_range <= 32:
+            raise ValueError("pan_range must be an integer in 0..32, got %r" % (pan_range,))
+        self.pan_range = int(pan_range)
+        self.last_pans = []                      # pan_range > 0: (global frame index, dx, dy) of the pairs that adopted a shift
+        self.last_pan_offsets = {}               # ... and {index into the last encode_range's records: (ox, oy)}: what the type-6 record says
+        if self.pan_range:
+            if not gop_batching:
+                raise ValueError("pan_range=%d needs gop_batching=True: the frame-by-frame route has no resident block to align" % self.pan_range)
+            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
+                raise ValueError("pan_range=%d acts on inter-frames: not with inter_frames=False or keyframe_interval=1" % self.pan_range)
+            if mask_channels != "all":
+                raise ValueError("pan_range=%d rolls every sample of a pixel: it needs mask_channels='all'" % self.pan_range)
+            if error_bounds is not None:
+                e = container.bounds_frame(error_bounds)
+                if e.ndim >= 2 and not bool((e.reshape((-1,) + e.shape[2:]) == e.reshape((-1,) + e.shape[2:])[0]).all()):
+                    raise ValueError("pan_range=%d moves the pixels: not with error_bounds that differ from pixel to pixel "
+                                     "(per-channel bounds are fine)" % self.pan_range)
         self.error_bounds = None
         if error_bounds is not None:
             if isinstance(max_error, (int, np.integer)) and not isinstance(max_error, bool) and max_error > 0:
@@ -437,13 +472,31 @@ class ImprovedVideoCompressor:
         t1 = time.perf_counter()
         coder.load_frames(block)                 # (synchronous: the frames are pageable host memory)
         t_up = time.perf_counter()
+        # what the block is looked at with before any hold rewrites it: a pixel the hold will keep still is not moving
+        tol = max_error if bounds is None else int(bounds.min())              # (the statistics are scalar: the smallest bound)
+        tol = min(tol if hold_mode == "first" else 2 * tol, (1 << (8 * sb)) - 1)
+        offsets, adopted = None, []              # pan_range: the frames' cumulative offsets (ox, oy), the pairs [(j, dx, dy)] that adopted a shift
+        if self.pan_range and W > 2 * self.pan_range and H > 2 * self.pan_range:
+            offsets, _, adopted = coder.align_pans(self.pan_range, tolerance=tol)     # everything below sees the stabilised block
+        t_pan = time.perf_counter()
         cuts = []
-        if self.scene_cuts:                      # before any hold rewrites the block; a pixel the hold will keep still is not moving
-            tol = max_error if bounds is None else int(bounds.min())          # (the statistic is scalar: the smallest bound)
-            tol = tol if hold_mode == "first" else 2 * tol
-            cuts = container.cut_frames(coder.cut_stats(tolerance=min(tol, (1 << (8 * sb)) - 1)), run_starts)
+        if self.scene_cuts:
+            cuts = container.cut_frames(coder.cut_stats(tolerance=tol), run_starts)
             if cuts:
-                coder.set_run_starts(sorted(set(run_starts) | set(cuts)))
+                starts = sorted(set(run_starts) | set(cuts))
+                coder.set_run_starts(starts)
+                if offsets is not None and any(offsets[j] != (0, 0) for j in cuts):
+                    # a cut is a keyframe, coded from the caller's array: its run is re-based -- the cut frame and the frames that hang
+                    # off it are rolled back by the cut frame's offset, so that the new run's offsets start at 0
+                    rel = [(0, 0)] * len(seg)
+                    for j in cuts:
+                        cx, cy = offsets[j]
+                        end = min([t for t in starts if t > j] + [len(seg)])
+                        for f in range(j, end):
+                            rel[f] = (-cx, -cy)
+                            offsets[f] = ((offsets[f][0] - cx) % W, (offsets[f][1] - cy) % H)
+                    coder.roll_frames(rel)
+                adopted = [row for row in adopted if row[0] not in cuts]      # (the pair in front of a cut is not coded)
         t2 = time.perf_counter()
         coder.encode()
         if self.profile_stages:
@@ -463,7 +516,9 @@ class ImprovedVideoCompressor:
         t5 = time.perf_counter()
         self._tm_add(stack=t1 - t0, upload=t_up - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
         if self.scene_cuts:
-            self._tm_add(cut_stats=t2 - t_up)    # (one launch sequence, a wait and 24 bytes per pair)
+            self._tm_add(cut_stats=t2 - t_pan)   # (one launch sequence, a wait and 24 bytes per pair)
+        if self.pan_range:
+            self._tm_add(pan_align=t_pan - t_up)
         if busy is not None:
             busy.append((t1, t5))
         n = H * W
@@ -471,6 +526,13 @@ class ImprovedVideoCompressor:
         out.digests = block_digests
         out.cuts = tuple(cuts)
         out.quality = block_quality
+        out.pan_offsets, out.pans = offsets, adopted
+        panned = [False] * len(res)              # pair f belongs to a run that carries a non-zero offset
+        if offsets is not None:
+            bounds_of_runs = sorted({0} | {f + 1 for f, r in enumerate(res) if r.get("skipped")}) + [len(seg)]
+            for lo, hi in zip(bounds_of_runs, bounds_of_runs[1:]):
+                if any(offsets[t] != (0, 0) for t in range(lo, hi)):
+                    panned[lo:hi - 1] = [True] * (hi - 1 - lo)
         broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
         for f, r in enumerate(res):
             if r.get("skipped"):                 # the pair in front of a keyframe
@@ -478,7 +540,7 @@ class ImprovedVideoCompressor:
                 out.append(None)
                 continue
             if int(uncovered[f]) or broken:      # chroma moved where luma did not: not representable.  With max_error > 0 the rest of the run
-                broken = bool(self._near)        # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have
+                broken = bool(self._near) or panned[f]       # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have (a panned run: the STABILISED frames)
                 out.append(None)
                 continue
             p = np.uint64(r["ones"]) / n
@@ -528,6 +590,13 @@ class ImprovedVideoCompressor:
                 raise ValueError("%s: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
                                  "another block's coder; make block_frames (%d) a multiple of keyframe_interval (%d) and start the range "
                                  "on a keyframe" % ("max_error=%d" % self.max_error if self.max_error else "error_bounds", off[0][0], self.block_frames, I))
+        if self.pan_range and blocks and inter_frames:
+            off = blocks_off_keyframes(blocks, first_index, I)
+            if off:
+                raise ValueError("pan_range=%d: the block that starts at frame %d does not start at a keyframe, so its cumulative offset would "
+                                 "need the pairs in front of it; make block_frames (%d) a multiple of keyframe_interval (%d) and start the "
+                                 "range on a keyframe" % (self.pan_range, off[0][0], self.block_frames, I))
+        pans, pan_table = [], {}                 # pan_range: (frame, dx, dy) of the adopted pairs; frame -> its cumulative offset, if not (0, 0)
         want = self.frame_digests
         digests = {}                             # frame -> its digest, or the future of the host twin's
         scene_cuts = []
@@ -579,6 +648,8 @@ class ImprovedVideoCompressor:
                 bd = getattr(inter, "digests", None)
                 cut = set(getattr(inter, "cuts", ()))                        # a cut frame is a run start of its block like a rule keyframe
                 scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
+                block_offsets = getattr(inter, "pan_offsets", None)
+                pans += [(lo + j, dx, dy) for j, dx, dy in getattr(inter, "pans", ()) if start <= lo + j < stop]
                 digest_of(lo, bd, 0)
                 for j in range(1, len(seg)):
                     u = lo + j
@@ -595,6 +666,8 @@ class ImprovedVideoCompressor:
                     elif inter[j - 1] is not None:
                         pending[u] = (inter_type, inter[j - 1])
                         digest_of(u, bd, j)
+                        if block_offsets is not None and block_offsets[j] != (0, 0) and start <= u < stop:
+                            pan_table[u - start] = block_offsets[j]
                         if inter.quality is not None:
                             quality[u] = inter.quality[j]
                         continue
@@ -613,6 +686,7 @@ class ImprovedVideoCompressor:
             tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
             self.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (digests[u] for u in range(start, stop))] if want else None
         self.last_scene_cuts = sorted(scene_cuts)
+        self.last_pans, self.last_pan_offsets = sorted(pans), pan_table
         self.last_quality = self._quality_dicts(frames, first_index, start, stop, quality) if self.quality_report else None
         _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
@@ -691,6 +765,8 @@ class ImprovedVideoCompressor:
             records = self.encode_range(frames, 0, 0, len(frames), inter_frames=use_inter)
         finally:
             self._release_lanes()                # (an exception in front of encode_range's own release)
+        if self.last_pan_offsets:                # the pan table: behind the last frame record, only when some frame is rolled
+            records = records + [(PANS, container.build_pans(self.last_pan_offsets))]
         if self.frame_digests:                   # the trailer: one digest per frame record, behind them all
             records = records + [(DIGESTS, build_trailer(self.last_digests))]
         self.last_compressed_frames = records
@@ -718,6 +794,8 @@ class ImprovedVideoCompressor:
             results["hold_mode"] = self.hold_mode
         if self.scene_cuts:
             results["scene_cuts"] = list(self.last_scene_cuts)
+        if self.pan_range:
+            results["pans"] = list(self.last_pans)
         if self.verbose:
             print("\\nCompression Results:")
             print(f"Original Size: {original_size / (1024 * 1024):.2f} MB")
@@ -749,7 +827,7 @@ class ImprovedVideoCompressor:
             records = [r if isinstance(r, tuple) else (KEY, r) for r in compressed_frames]
         if not records:
             raise ValueError("No compressed frames provided")
-        records, stored = container.split_trailer(records)                   # (a damaged trailer is a plain ValueError here: not a damaged frame)
+        records, pan_table, stored = container.split_tables(records)         # (a damaged trailer or pan table is a plain ValueError here: not a damaged frame)
         if not records:
             raise ValueError("No compressed frames provided")
         expected = stored if self.verify_digests else None
@@ -789,6 +867,11 @@ class ImprovedVideoCompressor:
                 for i, f in enumerate(decoded_frames):
                     got[first + i] = (frame_digest_host(frame_data(f)), "host")
 
+        def run_offsets(lo, hi):
+            """The cumulative pan offsets of the records lo .. hi-1, or None when none of them is rolled."""
+            offs = [pan_table.get(i, (0, 0)) for i in range(lo, hi)]
+            return offs if any(o != (0, 0) for o in offs) else None
+
         def run_job(job, take):
             k, lo, hi = job
             base = keys[k].result()[0] if types[k] == KEY else None          # (waits for the host's inflate without holding a lane)
@@ -798,7 +881,7 @@ class ImprovedVideoCompressor:
                 if lo is None:
                     return None
                 return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi],
-                                        digests_out=dev_digest(lo, hi - lo))
+                                        digests_out=dev_digest(lo, hi - lo), offsets=run_offsets(lo, hi))
         try:
             bases = {k for k, _, _ in runs}
             jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty == KEY_RICE and j not in bases]     # lone type-3 keyframes: no run
@@ -825,8 +908,9 @@ class ImprovedVideoCompressor:
                 if i in decoded:
                     frames += decoded[i]
                 else:
-                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]])
-                    host_digests(i, frames[i:ends[i]])
+                    stabilised = []
+                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]], run_offsets(i, ends[i]), stabilised)
+                    host_digests(i, stabilised)                              # (the digests describe the frames the records code)
                 i = ends[i]
         finally:
             key_pool.shutdown(wait=True)
@@ -845,8 +929,10 @@ class ImprovedVideoCompressor:
             print(f"Decompressed {len(frames)} frames in {time.time() - start:.2f} seconds")
         return frames
 
-    def _decode_frame_by_frame(self, base, records):
-        """The frames of a run of inter-frame records after `base`, one record at a time (gop_batching=False)."""
+    def _decode_frame_by_frame(self, base, records, offsets=None, stabilised_out=None):
+        """The frames of a run of inter-frame records after `base`, one record at a time (gop_batching=False).  offsets: the records'
+        cumulative pan offsets (ox, oy), or None -- the records code the STABILISED frames, each is rolled back on the host (np.roll)
+        after the next record has been applied to it; stabilised_out: a list that receives the frames as the records code them."""
         frames = []
         for ty, r in records:
             if ty == INTER_RICE:
@@ -856,7 +942,18 @@ class ImprovedVideoCompressor:
                 mask, values = self.inter._decompress_frame_differences(r[1:], base.shape, dtype=dtype)
                 frames.append(self.inter._apply_frame_diff(base, mask, values))
             base = frames[-1]
-        return frames
+        if stabilised_out is not None:
+            stabilised_out += frames
+        if offsets is None:
+            return frames
+        container.check_pans({i: o for i, o in enumerate(offsets)}, frame_data(base).shape)
+        out = []
+        for f, (ox, oy) in zip(frames, offsets):
+            if (ox, oy) != (0, 0):
+                a = np.roll(frame_data(f), (oy, ox), axis=(0, 1))            # F(p) = S((p - c) mod (W, H))
+                f = YUVFrame(a) if isinstance(f, YUVFrame) else a
+            out.append(f)
+        return out
 
     @staticmethod
     def _parse_run(base_arr, recs, types):
@@ -892,13 +989,17 @@ class ImprovedVideoCompressor:
                     raise ValueError("changed_values does not match the mask")
                 masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None):
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None, offsets=None):
         """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
         ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
         rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
         (default: lane 0); pool: executor for the inflates (default: a temporary one); types: the records' types (default: all type 2);
         digests_out: a list that receives the digest of every rebuilt frame, in order -- taken on the device from the chain block, after
-        the rebuild of a chunk and before its download (engine.rebuild_chain's hook)."""
+        the rebuild of a chunk and before its download (engine.rebuild_chain's hook).
+        offsets: None, or the records' cumulative pan offsets (ox, oy): the records code the stabilised frames S(p) = F((p + c) mod (W, H)),
+        so every rebuilt chunk is rolled back on the device (rbf_roll_frames with the negated offsets) after the digest hook and before
+        its download -- after its last frame, still stabilised, has been copied into the chain block's slot 0 for the next chunk."""
+        from . import _native as nat
         from .engine import apply_chain
         if lane is None:
             lane = self._get_lanes(1)[0]
@@ -931,16 +1032,37 @@ class ImprovedVideoCompressor:
         out, prev, i = [], base_arr, 0
         hook = None if digests_out is None else (lambda ptr, fbytes, cnt: digests_out.extend(int(x) for x in lane.digests(ptr, fbytes, cnt, fbytes)))
         chunk = self.chain_chunk_frames
+        fbytes, pixel_bytes = base_arr.nbytes, base_arr.nbytes // n
+        if offsets is not None:
+            container.check_pans({k: o for k, o in enumerate(offsets)}, base_arr.shape)
+
+        def unroll_from(i0):
+            """rebuild_chain's before_download hook for the stretch that starts at record i0 of the run."""
+            if offsets is None:
+                return None
+
+            def unroll(fb, c0, cnt):
+                offs = offsets[i0 + c0:i0 + c0 + cnt]
+                if not any(o != (0, 0) for o in offs):
+                    return False
+                L = nat.lib()
+                nat.check(L.rbf_memcpy_d2d(lane.ctx.handle, fb.ptr, fb.ptr + cnt * fbytes, fbytes))      # the next chunk's predecessor: still stabilised
+                neg = (nat._i32 * (2 * cnt))(*[-int(v) for o in offs for v in o])
+                nat.check(L.rbf_roll_frames(lane.ctx.handle, fb.ptr + fbytes, fbytes, cnt, W, H, pixel_bytes, neg))
+                return True
+            return unroll
         while i < len(parsed):                   # stretches of one record type: values written (type 2) or residuals added (type 4)
             j = i
             while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
                 j += 1
             if parsed[i]["rice"]:
-                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook)
+                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=unroll_from(i))
             else:
-                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook)
+                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=unroll_from(i))
             out += part
             prev, i = part[-1], j
+            if offsets is not None and i < len(parsed) and offsets[i - 1] != (0, 0):      # the next stretch continues the stabilised frame
+                prev = np.ascontiguousarray(np.roll(prev, (-offsets[i - 1][1], -offsets[i - 1][0]), axis=(0, 1)))
         t5 = time.perf_counter()
         self._tm_add(parse=t1 - t0, mask_decode=t2 - t1, inflate_wait=t3 - t2, check=t4 - t3, apply_chain=t5 - t4)
         if busy is not None:

@@ -1,0 +1,364 @@
+"""Pan alignment on the GPU: rbf_pan_search (k_pan_sad's tiles and ragged grids, the device-side pick, the cyclic moving counts) equals the
+numpy reference (pan_ref.py) in every number of every pair, rbf_roll_frames equals np.roll on both of its paths, GopCoder.align_pans
+leaves the reference's stabilised block behind, and ImprovedVideoCompressor(pan_range=R) keeps a panning clip's inter-frames in
+containers a fresh default compressor decodes -- bit-exactly, or within the bound of a near-lossless call."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import pan_ref
+from new_bloom_filter_repo_amd import _native as nat
+from new_bloom_filter_repo_amd import container
+from new_bloom_filter_repo_amd.container import INTERS, KEYS, PANS
+from new_bloom_filter_repo_amd.gop import GopCoder
+from new_bloom_filter_repo_amd.integrity import IntegrityError
+from new_bloom_filter_repo_amd.synthetic import make_camera_gop, make_panning_gop
+from new_bloom_filter_repo_amd.verify import quality, verify_max_error
+from new_bloom_filter_repo_amd.video_compressor import ImprovedVideoCompressor
+
+pytestmark = pytest.mark.gpu
+
+POISON = 0xFF
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = nat.Context(0)
+    yield c
+    c.close()
+
+
+def as_rows(ref_rows):
+    out = np.zeros(len(ref_rows), dtype=nat.PAN_ROW)
+    for i, r in enumerate(ref_rows):
+        for k, v in r.items():
+            out[i][k] = v
+    return out
+
+
+def search(ctx, frames, R, tolerance=0, run_starts=None, pad=0, **override):
+    """Lay the frames out on the device (frame f at f * (frame bytes + pad)), call rbf_pan_search with an `out` full of 0xFF and return
+    (rc, out as PAN_ROW rows).  override: arguments to replace (width, height, channels, sample_bytes, range, tolerance, nframes, out)."""
+    x = np.stack(frames)
+    F, H, W = x.shape[:3]
+    C = x.shape[3] if x.ndim == 4 else 1
+    sb = x.dtype.itemsize
+    fb = H * W * C * sb
+    host = np.full(F * (fb + pad), POISON, dtype=np.uint8)
+    raw = x.reshape(F, -1).view(np.uint8)
+    for f in range(F):
+        host[f * (fb + pad):f * (fb + pad) + fb] = raw[f]
+    a = dict(width=W, height=H, channels=C, sample_bytes=sb, range=R, tolerance=tolerance, nframes=F)
+    a.update(override)
+    out = np.full(max(1, F - 1) * nat.PAN_ROW.itemsize, POISON, dtype=np.uint8)
+    starts = None
+    if run_starts is not None:
+        starts = (ctypes.c_uint8 * F)(*[1 if t in run_starts else 0 for t in range(F)])
+    buf = ctx.alloc(host.size)
+    try:
+        buf.upload(host)
+        rc = nat.lib().rbf_pan_search(ctx.handle, buf.ptr, fb + pad, a["nframes"], a["width"], a["height"], a["channels"], a["sample_bytes"],
+                                      a["range"], a["tolerance"], starts, None if "out" in override else out.ctypes.data)
+    finally:
+        buf.free()
+    return rc, out.view(nat.PAN_ROW)[:F - 1]
+
+
+SHAPES = [(96, 64, 4), (67, 33, 4), (50, 40, 16), (80, 72, 32), (320, 180, 8)]
+
+
+@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d_R%d" % s)
+def test_search_equals_the_reference(ctx, shape, dtype, C):
+    """Planted shifts at the four corners of the range, (0, 0), (1, 0) and (0, -1); whole tiles, ragged tiles, one grid row, R = 32."""
+    W, H, R = shape
+    frames, shifts = pan_ref.planted_clip(W, H, R, dtype, channels=C, nframes=8)
+    for tol, pad in ((0, 0), (3, 2 * dtype().itemsize)):
+        rc, got = search(ctx, frames, R, tol, pad=pad)
+        assert rc == 0, nat.lib().rbf_last_error()
+        want = as_rows(pan_ref.stat_rows(frames, R, tol))
+        assert np.array_equal(got, want), (got, want)
+    if shape in ((96, 64, 4), (320, 180, 8)):                          # (test_pan_cpu.py: the reference finds them on these)
+        assert [(int(r["dx"]), int(r["dy"])) for r in got] == shifts
+
+
+def test_search_16_bit_extremes_and_64_bit_sums(ctx):
+    W, H, R = 320, 180, 8
+    a, b = np.zeros((H, W), dtype=np.uint16), np.full((H, W), 65535, dtype=np.uint16)
+    for tol, moving in ((65534, W * H), (65535, 0)):
+        rc, got = search(ctx, [a, b, a], R, tol)
+        assert rc == 0
+        points = len(range(R, W - R, 8)) * len(range(R, H - R, 8))
+        for r in got:                                                  # every candidate ties: (0, 0) wins
+            assert (r["dx"], r["dy"], r["sad_zero"], r["sad_best"], r["moving_zero"], r["moving_best"]) == (0, 0, points * 65535, points * 65535, moving, moving)
+    # more than 65536 grid points x 65535: the sums need more than 32 bits.  One candidate, (-2, 3), sees frame f-1's zeros again.
+    W, H = 2072, 2064
+    prev, cur = np.zeros((H, W), dtype=np.uint16), np.full((H, W), 65535, dtype=np.uint16)
+    xs, ys = pan_ref.grid_points(W, H, R)
+    assert len(xs) * len(ys) * 65535 > 1 << 32
+    cur[np.ix_(ys + 3, xs - 2)] = 0
+    rc, got = search(ctx, [prev, cur], R, 0)
+    assert rc == 0
+    want = as_rows(pan_ref.stat_rows([prev, cur], R, 0))
+    assert np.array_equal(got, want) and int(want[0]["sad_zero"]) == len(xs) * len(ys) * 65535 and (want[0]["dx"], want[0]["dy"], want[0]["sad_best"]) == (-2, 3, 0)
+
+
+def test_search_run_starts_and_reused_scratch(ctx):
+    """Rows in front of run starts are zeros; a small call after a large one (and the same call twice) sees no stale partial sums."""
+    big, _ = pan_ref.planted_clip(320, 180, 8, np.uint8, nframes=8)
+    small, _ = pan_ref.planted_clip(67, 33, 4, np.uint8, nframes=8)
+    rc, got = search(ctx, big, 8, 0, run_starts=[3, 4, 7])
+    assert rc == 0 and np.array_equal(got, as_rows(pan_ref.stat_rows(big, 8, 0, run_starts=[3, 4, 7])))
+    assert all(not any(int(v) for v in got[j]) for j in (2, 3, 6))
+    want = as_rows(pan_ref.stat_rows(small, 4, 1, run_starts=[2]))
+    for _ in range(2):
+        rc, got = search(ctx, small, 4, 1, run_starts=[2])
+        assert rc == 0 and np.array_equal(got, want)
+    rc, got = search(ctx, small, 2, 0, run_starts=[0])                    # (frame 0 always starts a run: its flag says nothing)
+    assert rc == 0 and np.array_equal(got, as_rows(pan_ref.stat_rows(small, 2, 0)))
+
+
+def test_search_refuses_bad_arguments_and_leaves_out_alone(ctx):
+    frames, _ = pan_ref.planted_clip(67, 33, 4, np.uint8, nframes=3)
+    for kw in (dict(range=0), dict(range=33), dict(range=16, height=32), dict(range=16, width=32), dict(range=17), dict(channels=0), dict(channels=5),
+               dict(sample_bytes=3), dict(sample_bytes=0), dict(tolerance=256), dict(width=0), dict(out=None)):
+        rc, out = search(ctx, frames, kw.pop("range", 4), **kw)
+        assert rc == nat.RBF_EINVAL and nat.lib().rbf_last_error(), kw
+        assert bool((out.view(np.uint8) == POISON).all()), kw
+    rc, out = search(ctx, frames[:1], 4)                                  # no pair: nothing to do
+    assert rc == 0
+    rc, out = search(ctx, [f.astype(np.uint16) for f in frames], 4, tolerance=65535)
+    assert rc == 0
+    rc, out = search(ctx, [f.astype(np.uint16) for f in frames], 4, tolerance=65536)
+    assert rc == nat.RBF_EINVAL and bool((out.view(np.uint8) == POISON).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the roll
+def roll_call(ctx, x, offsets, pad=0):
+    """x: (F, H, W, pixel_bytes) uint8.  Returns (rc, the block after the call as (F, frame bytes + pad) uint8)."""
+    F, H, W, pb = x.shape
+    fb = H * W * pb
+    host = np.full((F, fb + pad), 0xA5, dtype=np.uint8)
+    host[:, :fb] = x.reshape(F, fb)
+    flat = (ctypes.c_int32 * (2 * F))(*[int(v) for o in offsets for v in o])
+    buf = ctx.alloc(host.size)
+    try:
+        buf.upload(host)
+        rc = nat.lib().rbf_roll_frames(ctx.handle, buf.ptr, fb + pad, F, W, H, pb, flat)
+        ctx.sync()
+        return rc, buf.download().reshape(F, fb + pad)
+    finally:
+        buf.free()
+
+
+def roll_offsets(W, H):
+    return [(0, 0), (1, 0), (W - 1, 0), (-1, 0), (W + 3, 0), (0, 1), (0, H - 1), (0, -1), (0, H + 3), (5, -7), (W, -H), (-W - 2, 2 * H + 1)]
+
+
+@pytest.mark.parametrize("pb", [1, 2, 3, 4, 6, 8])
+@pytest.mark.parametrize("shape", [(67, 33), (64, 16)], ids=["67x33", "64x16"])
+@pytest.mark.parametrize("pad", [0, 48, 5])
+def test_roll_equals_numpy(ctx, shape, pb, pad):
+    """67 x 33: no row is a multiple of 16 bytes (pb = 1..8 with W = 67 except pb = 16k): the byte-wise path; 64 x 16: every row is, and the
+    wrap point falls inside a vector whenever ox * pb is no multiple of 16.  Twelve frames: more than one chunk of the scratch."""
+    W, H = shape
+    offs = roll_offsets(W, H)
+    rng = np.random.default_rng(W * 100 + pb)
+    x = rng.integers(0, 256, (len(offs), H, W, pb), dtype=np.uint8)
+    rc, got = roll_call(ctx, x, offs, pad)
+    assert rc == 0, nat.lib().rbf_last_error()
+    fb = H * W * pb
+    assert bool((got[:, fb:] == 0xA5).all()), "the bytes between the frames are never written"
+    want = np.stack([pan_ref.roll(f, ox, oy) for f, (ox, oy) in zip(x, offs)])
+    assert np.array_equal(got[:, :fb].reshape(x.shape), want)
+    assert np.array_equal(want[0], x[0]) and np.array_equal(want[10], x[10])          # reduced offsets of zero
+    rc, back = roll_call(ctx, want, [(-ox, -oy) for ox, oy in offs], pad)             # the negated roll is the inverse
+    assert rc == 0 and np.array_equal(back[:, :fb].reshape(x.shape), x)
+
+
+def test_roll_interleaved_shapes_and_refusals(ctx):
+    rng = np.random.default_rng(1)
+    for H, W, C, dt in ((33, 67, 3, np.uint8), (16, 64, 4, np.uint8), (33, 67, 3, np.uint16), (16, 64, 4, np.uint16)):
+        x = rng.integers(0, np.iinfo(dt).max, (4, H, W, C), dtype=dt)
+        offs = [(3, 0), (0, 0), (W - 5, 2), (-4, -1)]
+        rc, got = roll_call(ctx, x.view(np.uint8).reshape(4, H, W, C * x.itemsize), offs)
+        assert rc == 0
+        want = np.stack([pan_ref.roll(f, ox, oy) for f, (ox, oy) in zip(x, offs)])
+        assert np.array_equal(got.reshape(-1).view(dt).reshape(x.shape), want)
+    x = np.zeros((2, 4, 4, 1), dtype=np.uint8)
+    buf = ctx.alloc(64)
+    offs = (ctypes.c_int32 * 4)(1, 1, 1, 1)
+    L = nat.lib()
+    try:
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 16, 2, 4, 4, 0, offs) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 16, 2, 4, 4, 9, offs) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 16, 2, 0, 4, 1, offs) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 15, 2, 4, 4, 1, offs) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, None, 16, 2, 4, 4, 1, offs) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 16, 2, 4, 4, 1, None) == nat.RBF_EINVAL
+        assert L.rbf_roll_frames(ctx.handle, buf.ptr, 16, 0, 4, 4, 1, None) == 0
+    finally:
+        buf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the coder
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+def test_coder_align_pans(ctx, dtype):
+    W, H, R = 96, 64, 4
+    frames, shifts = pan_ref.planted_clip(W, H, R, dtype)
+    stab, offs, adopted, rows = pan_ref.stabilise(frames, R, 0, run_starts=[6])
+    with GopCoder(ctx, W, H, 12, channels=3, sample_bytes=np.dtype(dtype).itemsize, mask_channels=3, run_starts=[6], keep_originals=True) as coder:
+        coder.load_frames(np.stack(frames))
+        got_offs, got_rows, got_adopted = coder.align_pans(R)
+        assert got_offs == offs and got_adopted == adopted and np.array_equal(got_rows, as_rows(rows))
+        assert offs[6] == (0, 0) and any(o != (0, 0) for o in offs)
+        block = coder.frames.numpy(ctx, coder.frame_bytes * 12)[:coder.frame_bytes * 12].view(dtype).reshape((12,) + frames[0].shape)
+        assert np.array_equal(block, np.stack(stab)), "the resident block is the reference's stabilised block"
+        coder.encode()
+        ones = [r["ones"] for r in coder.results()]
+        want = [0 if j == 6 else rows[j - 1]["moving_best" if any(a[0] == j for a in adopted) else "moving_zero"] for j in range(1, 12)]
+        assert ones == want, "pair f of the stabilised block differs in exactly moving(v_f) pixels"
+        err = coder.error_stats()
+        assert not err["differing"].any() and not err["sse"].any(), "the originals were rolled with the block"
+    with pytest.raises(ValueError, match="planar_luma"):
+        with GopCoder(ctx, W, H, 3, planar_luma=True) as coder:
+            coder.align_pans(R)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the surface
+I, T = 6, 12
+_cache = {}
+
+
+def clip(noise=0):
+    if noise not in _cache:
+        _cache[noise] = pan_ref.planted_clip(96, 64, 4, np.uint8, sensor_noise=noise)
+    return _cache[noise]
+
+
+def encode(frames, **kw):
+    kw.setdefault("keyframe_interval", I)
+    kw.setdefault("mask_channels", "all")
+    comp = ImprovedVideoCompressor(**kw)
+    try:
+        res = comp.compress_video([f.copy() for f in frames], input_color_space="YUV")
+        return res, comp.last_compressed_frames, ImprovedVideoCompressor._container(comp.last_compressed_frames), comp
+    finally:
+        comp.close()
+
+
+def decode(blob, chunk=None, **kw):
+    fresh = ImprovedVideoCompressor(**kw)
+    if chunk:
+        fresh.chain_chunk_frames = chunk
+    try:
+        dec = fresh.decompress_video(compressed_frames=ImprovedVideoCompressor._parse_container(blob))
+        return [np.asarray(getattr(d, "data", d)) for d in dec], fresh.last_integrity
+    finally:
+        fresh.close()
+
+
+def kinds(records):
+    return "".join("K" if ty in KEYS else "i" if ty in INTERS else "P" if ty == PANS else "D" for ty, _ in records)
+
+
+def planted_pans(shifts):
+    return [(j, dx, dy) for j, (dx, dy) in enumerate(shifts, start=1) if (dx, dy) != (0, 0) and j % I]
+
+
+@pytest.mark.parametrize("block", [12, 6])
+@pytest.mark.parametrize("codec", ["rice", "zlib"])
+def test_surface_round_trip(codec, block):
+    frames, shifts = clip()
+    res, records, blob, comp = encode(frames, sample_codec=codec, pan_range=4, block_frames=block)
+    assert comp.last_pans == planted_pans(shifts) == res["pans"]
+    assert kinds(records) == "KiiiiiKiiiiiP"
+    table = dict((i, (ox, oy)) for i, ox, oy in container.parse_pans(records[-1][1]))
+    _, offs, _, _ = pan_ref.stabilise(frames, 4, 0, run_starts=[6])
+    assert table == {j: o for j, o in enumerate(offs) if o != (0, 0)} == comp.last_pan_offsets
+    for kw in (dict(), dict(chunk=2), dict(gop_batching=False), dict(chunk=2, gpu_lanes=1)):
+        dec, _ = decode(blob, **kw)
+        assert len(dec) == T and all(np.array_equal(d, f) for d, f in zip(dec, frames)), kw
+    res0, records0, blob0, _ = encode(frames, sample_codec=codec, pan_range=0, block_frames=block)
+    assert "pans" not in res0 and kinds(records0) == "KiiiiiKiiiii"
+    print("container bytes: pan_range=4 %d, pan_range=0 %d" % (len(blob), len(blob0)))
+    assert len(blob) < len(blob0)                                      # (test_pan_cpu.py: the masks fall from about n to under 0.15 n)
+    _, _, blob_default, _ = encode(frames, sample_codec=codec, block_frames=block)      # the unchanged path: no keyword at all
+    assert blob0 == blob_default
+    if block == 6:
+        for lanes in (1, 3):                                           # (the default is two lanes)
+            assert encode(frames, sample_codec=codec, pan_range=4, block_frames=6, gpu_lanes=lanes)[2] == blob
+
+
+@pytest.mark.parametrize("codec", ["rice", "zlib"])
+def test_surface_static_clip_writes_todays_bytes(codec):
+    for noise, kw in ((0, dict()), (1, dict(max_error=2))):
+        frames = make_camera_gop(4, 96, 64, T, sensor_noise=noise)
+        res, records, blob, comp = encode(frames, sample_codec=codec, pan_range=4, **kw)
+        assert comp.last_pans == [] and res["pans"] == [] and "P" not in kinds(records)
+        assert blob == encode(frames, sample_codec=codec, **kw)[2]
+    small = make_camera_gop(4, 8, 8, T)                                # frames not larger than 2R: coded as without the keyword
+    assert encode(small, pan_range=4)[2] == encode(small)[2]
+
+
+@pytest.mark.parametrize("near", [dict(max_error=2), dict(max_error=1, hold_mode="lookahead")], ids=["first", "lookahead"])
+def test_surface_near_lossless(near):
+    frames, shifts = clip(noise=1)
+    res, records, blob, comp = encode(frames, sample_codec="rice", pan_range=4, **near)
+    assert comp.last_pans == planted_pans(shifts) and kinds(records) == "KiiiiiKiiiiiP"
+    dec, _ = decode(blob, chunk=2)
+    v = verify_max_error(frames, dec, near["max_error"], keyframe_interval=I)
+    assert v["within_bound"] and v["keyframes_exact"] and 0 < v["max_abs_error"] <= near["max_error"], v
+    assert len(blob) < len(encode(frames, sample_codec="rice", pan_range=0, **near)[2])
+
+
+def test_surface_digests_and_quality():
+    frames, shifts = clip()
+    res, records, blob, comp = encode(frames, sample_codec="rice", pan_range=4, frame_digests=True, quality_report=True)
+    assert kinds(records) == "KiiiiiKiiiiiPD"
+    dec, integrity = decode(blob, chunk=2)
+    assert integrity["frames"] == T == integrity["checked"] and all(np.array_equal(d, f) for d, f in zip(dec, frames))
+    dec, integrity = decode(blob, gop_batching=False)
+    assert integrity["checked"] == T and all(np.array_equal(d, f) for d, f in zip(dec, frames))
+    assert comp.last_quality == quality(frames, dec)
+    parsed = ImprovedVideoCompressor._parse_container(blob)
+    at = kinds(parsed).index("P")
+    for flip in (9, 13, len(parsed[at][1]) - 1):                       # one flipped byte in the table: a plain ValueError
+        body = bytearray(parsed[at][1])
+        body[flip] ^= 1
+        bad = parsed[:at] + [(PANS, bytes(body))] + parsed[at + 1:]
+        with pytest.raises(ValueError, match="pan table") as e:
+            decode(ImprovedVideoCompressor._container(bad))
+        assert not isinstance(e.value, IntegrityError)
+    # one flipped byte in the filter of an inter-frame of a panned run (zlib values: a mask that no longer fits them leaves the frame as its
+    # predecessor, frame_codec's rule for colour frames): the frame is not the one that was coded
+    _, _, blobz, compz = encode(frames, sample_codec="zlib", pan_range=4, frame_digests=True)
+    parsed = ImprovedVideoCompressor._parse_container(blobz)
+    j = min(compz.last_pan_offsets)
+    rec = bytearray(parsed[j][1])                                      # '<B' sample bytes | p, n, k, bits, bits, size = 28 bytes | the filter
+    rec[29 + 11] ^= 0xFF
+    with pytest.raises(IntegrityError):
+        decode(ImprovedVideoCompressor._container(parsed[:j] + [(parsed[j][0], bytes(rec))] + parsed[j + 1:]))
+    near = encode(clip(1)[0], sample_codec="rice", pan_range=4, max_error=2, quality_report=True, frame_digests=True)
+    dec, integrity = decode(near[2])
+    assert integrity["checked"] == T and near[3].last_quality == quality(clip(1)[0], dec, 2)
+
+
+def test_surface_scene_cut_inside_a_panned_run():
+    a = make_panning_gop(11, 96, 64, T, (2, 1))
+    b = make_panning_gop(12, 96, 64, T, (2, 1))
+    frames = a[:7] + b[7:]
+    stab, offs, adopted, _ = pan_ref.stabilise(frames, 4)
+    assert offs[7] != (0, 0)                                           # the cut frame carries an offset: its run has to be re-based
+    for codec in ("rice", "zlib"):
+        res, records, blob, comp = encode(frames, sample_codec=codec, pan_range=4, scene_cuts=True, keyframe_interval=T, block_frames=T,
+                                          frame_digests=True)
+        assert comp.last_scene_cuts == [7] and kinds(records) == "KiiiiiiKiiiiPD"
+        assert comp.last_pans == [p for p in adopted if p[0] != 7]
+        assert all(comp.last_pan_offsets.get(j, (0, 0)) == ((offs[j][0] - offs[7][0]) % 96, (offs[j][1] - offs[7][1]) % 64) for j in range(8, T))
+        dec, integrity = decode(blob, chunk=2)
+        assert integrity["checked"] == T and all(np.array_equal(d, f) for d, f in zip(dec, frames))
+        res0, records0, _, comp0 = encode(frames, sample_codec=codec, pan_range=0, scene_cuts=True, keyframe_interval=T, block_frames=T)
+        assert res0["keyframes"] > res["keyframes"] == 2
