@@ -147,6 +147,53 @@ def pan_offsets(stats, run_starts, W, H):
     return offsets, adopted
 
 
+def stat_tolerance(max_error, bounds_min, hold_mode, sample_bytes):
+    """The scalar tolerance a block is looked at with (GopCoder.cut_stats, align_pans) before any hold rewrites it -- a pixel the hold
+    will keep still is not moving: max_error, or the SMALLEST entry of the bound frame (bounds_min; None without one), doubled for
+    hold_mode="lookahead" and clamped to the sample range."""
+    tol = int(max_error if bounds_min is None else bounds_min)
+    return min(tol if hold_mode == "first" else 2 * tol, (1 << (8 * sample_bytes)) - 1)
+
+
+def rebase_cuts(offsets, cuts, starts, W, H):
+    """A scene cut is a keyframe, coded from the caller's array, so its run starts at offset 0 like every other: (new offsets, rel) for
+    a block whose frames were rolled by `offsets` (pan_offsets) and in which the frames `cuts` then became run starts (starts: all the
+    run starts, cuts included).  The cut frame and the frames that hang off it -- up to the next run start -- are rolled back by the cut
+    frame's offset: rel[f] is what to roll frame f by now (GopCoder.roll_frames; (0, 0) outside the cuts' runs), new offsets[f] the
+    frame's offset after that, reduced to 0 <= ox < W, 0 <= oy < H."""
+    new, rel = list(offsets), [(0, 0)] * len(offsets)
+    for j in cuts:
+        cx, cy = offsets[j]
+        end = min([t for t in starts if t > j] + [len(offsets)])
+        for f in range(j, end):
+            rel[f] = (-cx, -cy)
+            new[f] = ((offsets[f][0] - cx) % W, (offsets[f][1] - cy) % H)
+    return new, rel
+
+
+def fallback_pairs(skipped, uncovered, offsets, near):
+    """Which pairs of a coded block are NOT written as inter-frames: [bool] per pair, pair f being frame f + 1 of the block.  skipped[f]:
+    the pair stands in front of a run start (the frame is a keyframe anyway); uncovered[f]: pixels of it changed that its mask cannot
+    say (a luma mask, chroma moved alone), so the frame falls back to an exact keyframe.  In a near-lossless block (near) and in a run
+    that carries a non-zero pan offset (offsets: the frames' cumulative offsets, or None) the rest of the run goes with it: its records
+    continue the HELD or STABILISED frames, not the exact keyframe a decoder will have.
+    Under today's refusals that propagation cannot be reached from the surface: near and pan_range both need mask_channels="all", whose
+    uncovered counts are all zero.  It stays because it is what makes relaxing that constraint safe."""
+    pairs = len(skipped)
+    panned = [False] * pairs                     # pair f belongs to a run that carries a non-zero offset
+    if offsets is not None:
+        run_bounds = sorted({0} | {f + 1 for f in range(pairs) if skipped[f]}) + [pairs + 1]
+        for lo, hi in zip(run_bounds, run_bounds[1:]):
+            if any(offsets[t] != (0, 0) for t in range(lo, hi)):
+                panned[lo:hi - 1] = [True] * (hi - 1 - lo)
+    out, broken = [], False                      # broken: a frame of this run fell back, and the rest of the run goes with it
+    for f in range(pairs):
+        falls = not skipped[f] and (bool(int(uncovered[f])) or broken)
+        broken = falls and (bool(near) or panned[f])
+        out.append(bool(skipped[f]) or falls)
+    return out
+
+
 def split_trailer(records):
     """(frame records, digests): the digests of a container's DIGESTS record, one per frame record, or None when it has none.  A plain
     ValueError -- never an integrity error, which speaks of frames -- when the trailer is not the last record, is there twice, does not

@@ -174,6 +174,8 @@ class GopCoder:
         self.stats = oalloc(8 * nat.STATS_PER_FRAME * self.pairs)
         self.params, self.k = (nat.FilterParams * self.pairs)(), (ctypes.c_double * self.pairs)()
         self.record = None
+        self.gop = 0                                  # the resident GOP encode_begin() last coded
+        self._values = self._voff = self._uncov = self._cut_stats = self._digests = None      # scratch blocks, allocated on first use
         self.bounds = None                            # the bound frame on the device
         if self.error_bounds is not None:
             self.bounds = alloc(self.frame_bytes)
@@ -225,6 +227,10 @@ class GopCoder:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _block_ptr(self, block, gop):
+        """Where resident GOP `gop` starts in a block of interleaved frames (self.frames, self.originals)."""
+        return block.ptr + gop * self.frame_bytes * self.F
 
     def load_frames(self, frames, gop=0):
         """Upload one GOP of interleaved (F, H, W, C) frames into slot `gop`.  With planar_luma the Y planes are extracted on
@@ -346,15 +352,15 @@ class GopCoder:
         self.ctx.sync()
         ones = self.ones.numpy(self.ctx)[:8 * self.pairs].view(np.uint64)
         total = int(ones.sum())
-        if getattr(self, "_values", None) is None or self._values.nbytes < max(8, total * self.C * self.sb):
+        if self._values is None or self._values.nbytes < max(8, total * self.C * self.sb):
             self._values = self._alloc(max(8, total * self.C * self.sb))
-        if getattr(self, "_voff", None) is None:
+        if self._voff is None:
             self._voff = self._alloc(8 * (self.pairs + 1))
             self._uncov = self._alloc(8 * self.pairs)
         if self.frames is None:
             raise ValueError("gather_values needs the interleaved frames (keep_interleaved=True)")
         nat.check(nat.lib().rbf_gather_values_batch(
-            self.ctx.handle, self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W, self.H, self.W * self.C * self.sb, self.C * self.sb,
+            self.ctx.handle, self._block_ptr(self.frames, self.gop), self.frame_bytes, self.F, self.W, self.H, self.W * self.C * self.sb, self.C * self.sb,
             self.sb, self.C, self.masks.ptr, self.mask_stride, self._values.ptr, total, self._voff.ptr,
             self._uncov.ptr if check_uncovered else None))
         self.ctx.sync()
@@ -373,7 +379,7 @@ class GopCoder:
         counts (results_packed()'s); codec: the SampleCoder of this coder's context.  A skipped pair gets the empty stream."""
         if self.frames is None:
             raise ValueError("rice_streams needs the interleaved frames (keep_interleaved=True)")
-        return codec.encode_inter(self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W, self.H,
+        return codec.encode_inter(self._block_ptr(self.frames, self.gop), self.frame_bytes, self.F, self.W, self.H,
                                   self.C, self.sb, self.masks.ptr, self.mask_stride, ones)
 
     def cut_stats(self, gop=0, tolerance=0):
@@ -387,9 +393,9 @@ class GopCoder:
         assert 0 <= gop < self.resident_gops
         if self.pairs < 1:
             return np.zeros((0, 3), dtype=np.uint64)
-        if getattr(self, "_cut_stats", None) is None:
+        if self._cut_stats is None:
             self._cut_stats = self._alloc(24 * self.pairs)
-        nat.check(nat.lib().rbf_cut_stats(self.ctx.handle, self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+        nat.check(nat.lib().rbf_cut_stats(self.ctx.handle, self._block_ptr(self.frames, gop), self.frame_bytes, self.F, self.W,
                                           self.H, self.C, self.sb, int(tolerance), self._cut_stats.ptr))
         self.ctx.sync()
         return self._cut_stats.numpy(self.ctx, 24 * self.pairs)[:24 * self.pairs].view(np.uint64).reshape(self.pairs, 3).copy()
@@ -404,7 +410,7 @@ class GopCoder:
         assert 0 <= gop < self.resident_gops
         rows = np.zeros(self.pairs, dtype=nat.PAN_ROW)
         if self.pairs:
-            nat.check(nat.lib().rbf_pan_search(self.ctx.handle, self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+            nat.check(nat.lib().rbf_pan_search(self.ctx.handle, self._block_ptr(self.frames, gop), self.frame_bytes, self.F, self.W,
                                                self.H, self.C, self.sb, int(pan_range), int(tolerance), self.run_starts, rows.ctypes.data))
         return rows
 
@@ -420,7 +426,7 @@ class GopCoder:
         flat = (ctypes.c_int32 * (2 * self.F))(*[int(v) for o in offsets for v in o])
         for block in (self.frames, self.originals):
             if block is not None:
-                nat.check(nat.lib().rbf_roll_frames(self.ctx.handle, block.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.F, self.W,
+                nat.check(nat.lib().rbf_roll_frames(self.ctx.handle, self._block_ptr(block, gop), self.frame_bytes, self.F, self.W,
                                                     self.H, self.C * self.sb, flat))
         self.mark_loaded(gop)                         # the block holds new input: a look-ahead hold runs after the roll, not before
 
@@ -445,9 +451,9 @@ class GopCoder:
         exactly, so this is the decoded clip's quality.  Valid after encode(); blocks until the rows are on the host."""
         if self.originals is None:
             raise ValueError("error_stats needs the uploaded frames: GopCoder(keep_originals=True)")
-        off = getattr(self, "gop", 0) * self.frame_bytes * self.F
         rows = np.zeros(self.F, dtype=nat.ERROR_ROW)
-        nat.check(nat.lib().rbf_error_stats(self.ctx.handle, self.originals.ptr + off, self.frame_bytes, self.frames.ptr + off, self.frame_bytes,
+        nat.check(nat.lib().rbf_error_stats(self.ctx.handle, self._block_ptr(self.originals, self.gop), self.frame_bytes,
+                                            self._block_ptr(self.frames, self.gop), self.frame_bytes,
                                             self.F, self.W, self.H, self.C, self.sb, None if self.bounds is None else self.bounds.ptr,
                                             self.max_error, rows.ctypes.data))
         return rows
@@ -460,9 +466,9 @@ class GopCoder:
         if self.frames is None:
             raise ValueError("frame_digests needs the interleaved frames (keep_interleaved=True)")
         from .integrity import digests_device
-        if getattr(self, "_digests", None) is None:
+        if self._digests is None:
             self._digests = self._alloc(8 * self.F)
-        return digests_device(self.ctx, self.frames.ptr + getattr(self, "gop", 0) * self.frame_bytes * self.F, self.frame_bytes, self.F,
+        return digests_device(self.ctx, self._block_ptr(self.frames, self.gop), self.frame_bytes, self.F,
                               self.frame_bytes, out=self._digests)
 
     def results_packed(self):

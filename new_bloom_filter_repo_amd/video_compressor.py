@@ -19,6 +19,7 @@ import struct
 import threading
 import time
 import zlib
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -26,10 +27,11 @@ import numpy as np
 from . import container
 from . import params as P
 from ._native import frame_geometry
-from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, PANS, blocks_off_keyframes, is_keyframe, plan_range
+from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, PANS, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
 from .integrity import IntegrityError, build_trailer, digests_device, frame_digest_host
 from .sample_codec import key_format, key_record, parse_key_record, stream_info
+from .surface_options import check_blocks, check_options
 
 _POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)   # numpy 1.x has no bitwise_count
 
@@ -75,17 +77,19 @@ class _Lane:
             self.scratch = BufferCache(self.ctx)
         return digests_device(self.ctx, ptr, stride, nframes, frame_bytes, out=self.scratch.get("digests", 8 * nframes))
 
-    def coder(self, W, H, F, C, sb, mask_channels=1, max_error=0, hold_mode="first", error_bounds=None, keep_originals=False):
+    def coder(self, spec):
+        """The lane's GopCoder(**spec), kept.  A compressor has one bound frame per frame shape and dtype (its _bound_frames), so that
+        pair stands for the frame in the key."""
         from .gop import GopCoder
-        key = (W, H, F, C, sb, mask_channels, max_error, hold_mode, id(error_bounds), keep_originals)      # (the compressor keeps its bound frames: ids are stable)
+        E = spec.error_bounds
+        key = spec._replace(error_bounds=None if E is None else (E.shape, E.dtype.str))
         c = self.coders.get(key)
         if c is None:
             if len(self.coders) >= 2:            # a stream has at most two block sizes (full blocks and its tail)
                 for old in self.coders.values():
                     old.close()
                 self.coders = {}
-            c = self.coders[key] = GopCoder(self.ctx, W, H, F, channels=C, sample_bytes=sb, mask_channels=mask_channels, max_error=max_error,
-                                                hold_mode=hold_mode, error_bounds=error_bounds, keep_originals=keep_originals)
+            c = self.coders[key] = GopCoder(self.ctx, **spec._asdict())
         return c
 
     def decode_engine(self):
@@ -104,15 +108,10 @@ class _Lane:
         for c in self.coders.values():
             c.close()
         self.coders = {}
-        if self.engine is not None:
-            self.engine.close()
-            self.engine = None
-        if self.samples is not None:
-            self.samples.close()
-            self.samples = None
-        if self.scratch is not None:
-            self.scratch.close()
-            self.scratch = None
+        for name in ("engine", "samples", "scratch"):
+            if getattr(self, name) is not None:
+                getattr(self, name).close()
+                setattr(self, name, None)
 
     def close(self):
         self.release()
@@ -147,13 +146,19 @@ class _LanePool:
             return list(gpu_pool.map(lambda job: fn(job, self.take), jobs))
 
 
-class _BlockRecords(list):
-    """What _encode_block returns: the per-pair list, with the block's frame digests (uint64 per frame of the block, or None)."""
-    digests = None
-    cuts = ()                                    # scene_cuts=True: the block indices the cut rule made run starts
-    pan_offsets = None                           # pan_range > 0: the frames' cumulative offsets (ox, oy) in the block, or None
-    pans = ()                                    # ... and [(block index, dx, dy)] of the pairs that adopted a shift
-    quality = None                               # quality_report=True: GopCoder.error_stats() of the block, a row per frame
+_CoderSpec = namedtuple("_CoderSpec", "width height nframes channels sample_bytes mask_channels max_error hold_mode error_bounds keep_originals")      # GopCoder's keywords
+
+
+class _BlockRecords:
+    """What _encode_block returns for a block the GPU coded."""
+
+    def __init__(self, pairs=(), digests=None, cuts=(), pan_offsets=None, pans=(), quality=None):
+        self.pairs = list(pairs)                 # per pair: the future of its inter-frame record, or None (needs a keyframe, or is one)
+        self.digests = digests                   # frame_digests=True: uint64 per frame of the block, or None
+        self.cuts = tuple(cuts)                  # scene_cuts=True: the block indices the cut rule made run starts
+        self.pan_offsets = pan_offsets           # pan_range > 0: the frames' cumulative offsets (ox, oy) in the block, or None
+        self.pans = pans                         # ... and [(block index, dx, dy)] of the pairs that adopted a shift
+        self.quality = quality                   # quality_report=True: GopCoder.error_stats() of the block, a row per frame
 
 
 def _union_seconds(intervals):
@@ -174,6 +179,134 @@ def _close_timing(tm, t_all, busy):
     tm["total"] = time.perf_counter() - t_all
     tm["gpu_busy"] = _union_seconds(busy)                                    # wall time during which at least one lane had a copy or a kernel in flight
     tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
+
+
+def _run_offsets(pan_table, lo, hi):
+    """The cumulative pan offsets of the records lo .. hi-1 of a container, or None when none of them is rolled."""
+    offs = [pan_table.get(i, (0, 0)) for i in range(lo, hi)]
+    return offs if any(o != (0, 0) for o in offs) else None
+
+
+class _DigestLog:
+    """The digests decompress_video takes of the frames it rebuilds, against the stored ones.  expected: the container's digests, or None
+    when there is nothing to check -- then nothing is taken."""
+
+    def __init__(self, expected):
+        self.expected, self.checking = expected, expected is not None
+        self.got, self.device = {}, {}           # record index -> (digest of the rebuilt frame, "device" | "host"); first record index -> the list a lane fills
+
+    def sink(self, first):
+        """A list for the device digests of the records first, first + 1, ..., or None when not checking."""
+        return self.device.setdefault(first, []) if self.checking else None
+
+    def host(self, first, frames):
+        """Digest `frames`, the frames of the records first, first + 1, ..., with the host twin."""
+        if self.checking:
+            for i, f in enumerate(frames):
+                self.got[first + i] = (frame_digest_host(frame_data(f)), "host")
+
+    def summary(self, nframes):
+        """(last_integrity, last_bad_frames) of a call that rebuilt nframes frames."""
+        self.got.update({first + i: (int(v), "device") for first, values in self.device.items() for i, v in enumerate(values)})
+        where = [w for _, w in self.got.values()]
+        integrity = {"frames": nframes, "checked": len(self.got), "device": where.count("device"), "host": where.count("host")}
+        return integrity, [i for i in sorted(self.got) if self.got[i][0] != self.expected[i]]
+
+
+class _RangeRecords:
+    """The bookkeeping of one encode_range call: what becomes of every frame of [start, stop) -- its record, or the job that makes it,
+    its digest, its row of the quality report, its pan offset -- and the call's cuts and pans.  comp: the compressor; pool: the executor
+    of the host's zlib-9 and digest jobs.
+      records    frame -> (type, record)
+      pending    frame -> (type, the future of its record; KEY: the callable that joins it)
+      gpu_keys   sample_codec="rice": the keyframes coded as type-3 records on the lanes, at the end
+      digests    frame -> its digest, or the future of the host twin's
+      quality    quality_report: frame -> its row of the block it was coded in
+      pan_table  pan_range: index into the range's records -> the frame's cumulative offset, if not (0, 0)
+      scene_cuts, pans   the cut frames; (frame, dx, dy) of the adopted pairs"""
+
+    def __init__(self, comp, frames, first_index, start, stop, pool):
+        self.comp, self.frames, self.first_index, self.start, self.stop, self.pool = comp, frames, first_index, start, stop, pool
+        self.inter_type = INTER_RICE if comp.sample_codec == "rice" else INTER
+        self.records, self.pending, self.digests, self.quality, self.pan_table = {}, {}, {}, {}, {}
+        self.gpu_keys, self.scene_cuts, self.pans = set(), [], []
+
+    def key(self, t):
+        """Frame t is a keyframe: on a lane later (a type-3 record can carry it) or in zlib-9 on the host threads from now on."""
+        if t in self.pending or t in self.gpu_keys:
+            return
+        frame = self.frames[t - self.first_index]
+        if self.comp.sample_codec == "rice" and key_format(frame) is not None:
+            self.gpu_keys.add(t)
+        else:
+            self.pending[t] = (KEY, self.comp.compressor.compress_frame_jobs(frame, self.pool.submit))
+
+    def digest_of(self, u, block_digests=None, j=0):
+        """Frame u's digest: entry j of its block's (taken on the GPU from the resident frames), else the host twin's of the caller's array."""
+        if not self.comp.frame_digests or u in self.digests or not self.start <= u < self.stop:
+            return
+        if block_digests is not None:
+            self.digests[u] = int(block_digests[j])
+        else:
+            self.digests[u] = self.pool.submit(frame_digest_host, frame_data(self.frames[u - self.first_index]))
+
+    def take_block(self, block, inter):
+        """File the frames of `block` = (lo, end, run starts) of the plan; inter: what _encode_block made of it, or None -- not
+        batchable, or gop_batching=False: frame by frame, here.
+        The block's digests describe its frames AFTER the hold.  The hold never writes a run's first frame (rbf_kernels_hold.h: "frame
+        first[y] is never written"), so the block's first frame and the keyframes inside it -- the run starts handed to the coder -- still
+        are the caller's originals, which is what their keyframe records code: their digests are taken from the block too.  Not so a
+        frame that falls back to a keyframe with max_error > 0: its record codes the original, the block holds the held frame -- the
+        host twin digests the original."""
+        comp, start, stop = self.comp, self.start, self.stop
+        lo, end, _ = block
+        seg = self.frames[lo - self.first_index:end - self.first_index]      # predecessor + the frames lo+1..end-1
+        got = inter if inter is not None else _BlockRecords()
+        cut = set(got.cuts)                      # a cut frame is a run start of its block like a rule keyframe
+        self.scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
+        self.pans += [(lo + j, dx, dy) for j, dx, dy in got.pans if start <= lo + j < stop]
+        self.digest_of(lo, got.digests, 0)
+        for j in range(1, len(seg)):
+            u = lo + j
+            if is_keyframe(u, self.first_index, comp.keyframe_interval) or j in cut:
+                self.key(u)
+                self.digest_of(u, got.digests, j)
+                continue
+            if inter is None:
+                self.digest_of(u)
+                rec = comp._encode_inter(seg[j - 1], seg[j])
+                if rec is not None:
+                    self.records[u] = (self.inter_type, rec)
+                    continue
+            elif inter.pairs[j - 1] is not None:
+                self.pending[u] = (self.inter_type, inter.pairs[j - 1])
+                self.digest_of(u, got.digests, j)
+                if got.pan_offsets is not None and got.pan_offsets[j] != (0, 0) and start <= u < stop:
+                    self.pan_table[u - start] = got.pan_offsets[j]
+                if got.quality is not None:
+                    self.quality[u] = got.quality[j]
+                continue
+            self.key(u)
+            self.digest_of(u, None if comp._near else got.digests, j)
+
+    def finish(self, release, tm, busy):
+        """Code the type-3 keyframes, wait for the host threads, set the compressor's last_* attributes; the range's [(type, record)]."""
+        comp, frames, first_index, start, stop = self.comp, self.frames, self.first_index, self.start, self.stop
+        if self.gpu_keys:
+            t_key = time.perf_counter()
+            for u, rec in comp._encode_keys_rice(frames, first_index, sorted(self.gpu_keys), busy).items():
+                self.records[u] = (KEY_RICE, rec)
+            if release:
+                comp._release_lanes()
+            tm["gpu_phase"] += time.perf_counter() - t_key
+        t_wait = time.perf_counter()
+        for u, (ty, fut) in self.pending.items():
+            self.records[u] = (ty, fut() if ty == KEY else fut.result())
+        tm["zlib_wait"] = time.perf_counter() - t_wait                       # what the host threads' zlib-9 still owed after the last block left the GPU
+        comp.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (self.digests[u] for u in range(start, stop))] if comp.frame_digests else None
+        comp.last_scene_cuts, comp.last_pans, comp.last_pan_offsets = sorted(self.scene_cuts), sorted(self.pans), self.pan_table
+        comp.last_quality = comp._quality_dicts(frames, first_index, start, stop, self.quality) if comp.quality_report else None
+        return [self.records[u] for u in range(start, stop)]
 
 
 class ImprovedVideoCompressor:
@@ -263,91 +396,30 @@ class ImprovedVideoCompressor:
         Needs gop_batching=True, inter-frames, keyframe_interval > 1, mask_channels="all" and blocks that start at keyframes (as
         max_error > 0 does); not with error_bounds that differ from pixel to pixel (the bound map would no longer sit on the pixels it
         was drawn for; per-channel bounds are fine).  A block whose frames are not larger than 2R in both directions is coded as
-        without the keyword.  last_pans lists (global frame index, dx, dy) for every pair of the last encode_range that adopted a shift."""
-        if isinstance(pan_range, bool) or not isinstance(pan_range, (int, np.integer)) or not 0 <= pan_range <= 32:
-            raise ValueError("pan_range must be an integer in 0..32, got %r" % (pan_range,))
-        self.pan_range = int(pan_range)
-        self.last_pans = []                      # pan_range > 0: (global frame index, dx, dy) of the pairs that adopted a shift
-        self.last_pan_offsets = {}               # ... and {index into the last encode_range's records: (ox, oy)}: what the type-6 record says
-        if self.pan_range:
-            if not gop_batching:
-                raise ValueError("pan_range=%d needs gop_batching=True: the frame-by-frame route has no resident block to align" % self.pan_range)
-            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
-                raise ValueError("pan_range=%d acts on inter-frames: not with inter_frames=False or keyframe_interval=1" % self.pan_range)
-            if mask_channels != "all":
-                raise ValueError("pan_range=%d rolls every sample of a pixel: it needs mask_channels='all'" % self.pan_range)
-            if error_bounds is not None:
-                e = container.bounds_frame(error_bounds)
-                if e.ndim >= 2 and not bool((e.reshape((-1,) + e.shape[2:]) == e.reshape((-1,) + e.shape[2:])[0]).all()):
-                    raise ValueError("pan_range=%d moves the pixels: not with error_bounds that differ from pixel to pixel "
-                                     "(per-channel bounds are fine)" % self.pan_range)
-        self.error_bounds = None
-        if error_bounds is not None:
-            if isinstance(max_error, (int, np.integer)) and not isinstance(max_error, bool) and max_error > 0:
-                raise ValueError("error_bounds and max_error > 0 are two ways to say the bound: give one")
-            container.bounds_frame(error_bounds)     # what can be refused without a frame is refused here
-            self.error_bounds = error_bounds
-        self._bound_frames = {}                  # (frame shape, dtype) -> (the bound frame, its uniform value or None)
-        self.quality_report = bool(quality_report)
-        self.last_quality = None                 # quality_report=True: one dict per frame of the last encode_range
-        self.scene_cuts = bool(scene_cuts)
-        self.last_scene_cuts = []                # scene_cuts=True: the frames the last encode_range made keyframes because they are cuts
-        if self.scene_cuts:
-            if not gop_batching:
-                raise ValueError("scene_cuts=True needs gop_batching=True: the frame-by-frame route has no resident block to look at")
-            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
-                raise ValueError("scene_cuts=True acts on inter-frames: not with inter_frames=False or keyframe_interval=1")
-        if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)) or max_error < 0:
-            raise ValueError("max_error must be a non-negative integer, got %r" % (max_error,))
-        self.max_error = int(max_error)
-        if hold_mode not in ("first", "lookahead"):
-            raise ValueError("hold_mode must be 'first' or 'lookahead', got %r" % (hold_mode,))
-        if hold_mode == "lookahead" and not self.max_error and self.error_bounds is None:
-            raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0 or error_bounds")
-        self.hold_mode = hold_mode
-        self.frame_digests, self.verify_digests = bool(frame_digests), bool(verify_digests)
-        self.last_digests = None                 # frame_digests=True: the digests of the last encode_range's frames, aligned with its records
-        self.last_integrity = None               # {"frames", "checked", "device", "host"} of the last decompress_video
-        self.last_bad_frames = None              # ... and the frames whose digest did not match (decompress_video(on_mismatch="collect"))
-        self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
-        self._near = "error_bounds" if self.error_bounds is not None else "max_error > 0" if self.max_error else None
-        if self._near:
-            if mask_channels != "all":
-                raise ValueError("%s holds every sample of a pixel: it needs mask_channels='all'" % self._near)
-            if inter_frames is False or max(1, int(keyframe_interval)) == 1:
-                raise ValueError("%s acts on inter-frames: not with inter_frames=False or keyframe_interval=1" % self._near)
-            if not gop_batching:
-                raise ValueError("%s needs gop_batching=True: the frame-by-frame route has no resident run to hold" % self._near)
-        if mask_channels not in ("luma", "all"):
-            raise ValueError("mask_channels must be 'luma' or 'all', got %r" % (mask_channels,))
-        if sample_codec not in ("zlib", "rice"):
-            raise ValueError("sample_codec must be 'zlib' or 'rice', got %r" % (sample_codec,))
-        if sample_codec == "rice" and inter_frames is False:
-            raise ValueError("sample_codec='rice' writes 'BFV2' records; inter_frames=False asks for 'BFVC', which holds zlib keyframes only")
-        self.sample_codec = sample_codec
-        self.mask_channels = mask_channels
-        self.inter_frames = inter_frames
-        self.noise_tolerance = noise_tolerance
-        self.keyframe_interval = max(1, int(keyframe_interval))
-        self.min_diff_threshold = min_diff_threshold
-        self.max_diff_threshold = max_diff_threshold
-        self.bloom_threshold_modifier = bloom_threshold_modifier
-        self.batch_size = batch_size
+        without the keyword.  last_pans lists (global frame index, dx, dy) for every pair of the last encode_range that adopted a shift.
+        What the last call left behind: last_compressed_frames -- [(type, record bytes)] of compress_video; of encode_range last_digests,
+        last_quality, last_scene_cuts and last_pans as above, and last_pan_offsets -- {index into its records: (ox, oy)}, what the
+        type-6 record says; of decompress_video last_integrity -- {"frames", "checked", "device", "host"} -- and last_bad_frames -- the
+        frames whose digest did not match (on_mismatch="collect"); of either last_timing -- seconds per stage (bench.py's e2e_surface
+        leg; profile_stages=True synchronises between the stages of a block so that it can tell them apart)."""
+        o = self._options = check_options(keyframe_interval, inter_frames, gop_batching, block_frames, gpu_lanes, mask_channels, sample_codec,
+                                          max_error, frame_digests, verify_digests, hold_mode, scene_cuts, error_bounds, quality_report, pan_range)
+        self.pan_range, self.error_bounds, self.quality_report, self.scene_cuts = o.pan_range, o.error_bounds, o.quality_report, o.scene_cuts
+        self.max_error, self.hold_mode, self._near = o.max_error, o.hold_mode, o.near
+        self.frame_digests, self.verify_digests = o.frame_digests, o.verify_digests
+        self.sample_codec, self.mask_channels, self.inter_frames = o.sample_codec, o.mask_channels, o.inter_frames
+        self.keyframe_interval, self.gop_batching, self.block_frames, self.gpu_lanes = o.keyframe_interval, o.gop_batching, o.block_frames, o.gpu_lanes
+        self.noise_tolerance, self.min_diff_threshold, self.max_diff_threshold = noise_tolerance, min_diff_threshold, max_diff_threshold
+        self.bloom_threshold_modifier, self.batch_size = bloom_threshold_modifier, batch_size
         self.num_threads = max(1, num_threads or min(64, os.cpu_count() or 1))     # zlib of keyframes / changed values
-        self.gop_batching = bool(gop_batching)
-        # default block: two keyframe intervals (a multiple of the interval: every block of a stream has the same shape), at most 128 frames.
-        # Small blocks start the host's zlib of the changed values early; the GPU's share of a block is a fraction of a millisecond either way.
-        self.block_frames = max(2, int(block_frames)) if block_frames else min(128, max(2, 2 * self.keyframe_interval if 2 * self.keyframe_interval <= 128 else self.keyframe_interval))
-        self.gpu_lanes = max(1, int(gpu_lanes))
-        self.use_direct_yuv = use_direct_yuv
-        self.verbose = verbose
+        self.use_direct_yuv, self.verbose = use_direct_yuv, verbose
+        self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
+        self.last_pans, self.last_pan_offsets, self.last_scene_cuts = [], {}, []
+        self.last_quality = self.last_digests = self.last_integrity = self.last_bad_frames = self.last_compressed_frames = self.last_timing = None
+        self.profile_stages = False
         self.compressor = FixedVideoCompressor(verbose=verbose)
-        self._ctx = ctx
-        self._inter = None
-        self.last_compressed_frames = None       # [(type, record bytes)] of the last compress_video call
-        self.last_timing = None                  # seconds per stage of the last encode_range / decompress_video (bench.py's e2e_surface leg)
-        self.profile_stages = False              # True: synchronise between the stages of a block so that last_timing can tell them apart (bench.py)
-        self._lanes = []
+        self._bound_frames = {}                  # (frame shape, dtype) -> (the bound frame, its uniform value or None)
+        self._ctx, self._inter, self._lanes = ctx, None, []
         self._tm_lock = threading.Lock()
 
     def close(self):
@@ -407,9 +479,7 @@ class ImprovedVideoCompressor:
     def _encode_inter(self, prev, curr):
         """Record bytes for frame `curr` against `prev`, or None when a keyframe is needed."""
         a, b = frame_data(prev), frame_data(curr)
-        if a.shape != b.shape or a.dtype != b.dtype or a.dtype not in (np.uint8, np.uint16):
-            return None
-        if a.ndim == 3 and (a.shape[2] < 3 or a.shape[2] > 4):
+        if a.shape != b.shape or a.dtype != b.dtype or a.dtype not in (np.uint8, np.uint16) or (a.ndim == 3 and not 3 <= a.shape[2] <= 4):
             return None
         mask, values, _ = self.inter._calculate_frame_diff(a, b, threshold=0.0)
         if self.mask_channels != "all" or a.ndim == 2:     # (the all-channel mask marks every change by construction)
@@ -435,79 +505,121 @@ class ImprovedVideoCompressor:
         return build_record(self.inter.wire_format, p, n, k, len(bitmap), np.packbits(bitmap).tobytes(), len(witness),
                             np.packbits(np.array(witness, dtype=np.uint8)).tobytes(), ones * C, stream)
 
-    def _encode_block(self, seg, pool, run_starts=(), lane=None, busy=None):
-        """Inter-frame records of one block of consecutive frames in one pass over the GPU: seg[0] is only read (a keyframe, or a
-        shard's halo frame), every other frame is coded against its predecessor -- except the frames named in `run_starts` (indices
-        into seg), which are keyframes of the stream: they start a new run and the pair in front of them is not coded.  One upload,
-        ONE rbf_encode_runs launch sequence for all the runs, ONE exact-size download of the packed record (rbf_pack_records), one
-        batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.  With
-        frame_digests the block's frames are digested where they lie, after the hold (GopCoder.frame_digests): the list's `digests`.
-        With scene_cuts the block is looked at right after its upload (GopCoder.cut_stats) and the frames the rule calls cuts are
-        added to the run starts: the list's `cuts`.
-        lane: the context and coders to use (default: lane 0); busy: list that receives the (start, end) time of this block's GPU work.
-        Returns a list of futures / None per pair (None = needs a keyframe, or is one), or None when the block cannot be batched
-        (mixed shapes or dtypes)."""
-        t0 = time.perf_counter()
+    @staticmethod
+    def _block_geometry(seg):
+        """(a, H, W, C, sb) of a block of frames -- its first frame's array and _native.frame_geometry of it -- or, as a str, the reason
+        the GPU cannot take the block in one piece."""
         data = [frame_data(f) for f in seg]
         a = data[0]
         if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] < 3):
-            return None
+            return "frames of %s with shape %r" % (a.dtype, a.shape)
         if any(d.shape != a.shape or d.dtype != a.dtype for d in data[1:]):
-            return None
+            return "mixed shapes or dtypes"
+        return (a,) + tuple(frame_geometry(a))
+
+    def _coder_spec(self, a, nframes):
+        """The GopCoder keywords for a block of `nframes` frames like `a`."""
         H, W, C, sb = frame_geometry(a)
-        if C > 4:                                # rbf_gather_values_batch carries at most 4 samples per pixel
-            return _BlockRecords([None] * (len(seg) - 1))
-        if lane is None:
-            lane = self._get_lanes(1)[0]
-        ctx = lane.ctx
         mc = C if self.mask_channels == "all" and C >= 2 else 1      # all-channel mask: every change is covered, no uncovered pass
         max_error, hold_mode, bounds = self.max_error, self.hold_mode, None
         if self.error_bounds is not None:
             bounds, d = self._bound_frame(a)
             if d is not None:                    # one value everywhere: today's scalar calls, today's bytes
                 max_error, hold_mode, bounds = d, self.hold_mode if d else "first", None
-        coder = lane.coder(W, H, len(seg), C, sb, mc, max_error, hold_mode, bounds, self.quality_report)
-        coder.set_run_starts(list(run_starts))
-        block = _as_block(data)
-        t1 = time.perf_counter()
+        return _CoderSpec(W, H, nframes, C, sb, mc, max_error, hold_mode, bounds, self.quality_report)
+
+    def _prepare_block(self, coder, block, run_starts, tol):
+        """Upload `block` into the coder and make it what the hold and the mask stage are to see: aligned (pan_range: GopCoder.align_pans),
+        looked at for cuts (scene_cuts: GopCoder.cut_stats, container.cut_frames -- the cuts join the run starts) and, where a cut carries
+        an offset, re-based (container.rebase_cuts).  tol: container.stat_tolerance -- the block is looked at before any hold rewrites
+        it, and a pixel the hold will keep still is not moving.  Returns (run starts, offsets, adopted, cuts, times): the frames'
+        cumulative offsets (ox, oy) or None, the pairs [(j, dx, dy)] that adopted a shift, the cut frames, and when the upload and the
+        alignment were done (time.perf_counter)."""
         coder.load_frames(block)                 # (synchronous: the frames are pageable host memory)
         t_up = time.perf_counter()
-        # what the block is looked at with before any hold rewrites it: a pixel the hold will keep still is not moving
-        tol = max_error if bounds is None else int(bounds.min())              # (the statistics are scalar: the smallest bound)
-        tol = min(tol if hold_mode == "first" else 2 * tol, (1 << (8 * sb)) - 1)
-        offsets, adopted = None, []              # pan_range: the frames' cumulative offsets (ox, oy), the pairs [(j, dx, dy)] that adopted a shift
-        if self.pan_range and W > 2 * self.pan_range and H > 2 * self.pan_range:
+        starts, offsets, adopted, cuts = list(run_starts), None, [], []
+        if self.pan_range and coder.W > 2 * self.pan_range and coder.H > 2 * self.pan_range:
             offsets, _, adopted = coder.align_pans(self.pan_range, tolerance=tol)     # everything below sees the stabilised block
         t_pan = time.perf_counter()
-        cuts = []
         if self.scene_cuts:
             cuts = container.cut_frames(coder.cut_stats(tolerance=tol), run_starts)
             if cuts:
                 starts = sorted(set(run_starts) | set(cuts))
                 coder.set_run_starts(starts)
                 if offsets is not None and any(offsets[j] != (0, 0) for j in cuts):
-                    # a cut is a keyframe, coded from the caller's array: its run is re-based -- the cut frame and the frames that hang
-                    # off it are rolled back by the cut frame's offset, so that the new run's offsets start at 0
-                    rel = [(0, 0)] * len(seg)
-                    for j in cuts:
-                        cx, cy = offsets[j]
-                        end = min([t for t in starts if t > j] + [len(seg)])
-                        for f in range(j, end):
-                            rel[f] = (-cx, -cy)
-                            offsets[f] = ((offsets[f][0] - cx) % W, (offsets[f][1] - cy) % H)
+                    offsets, rel = container.rebase_cuts(offsets, cuts, starts, coder.W, coder.H)
                     coder.roll_frames(rel)
                 adopted = [row for row in adopted if row[0] not in cuts]      # (the pair in front of a cut is not coded)
+        return starts, offsets, adopted, cuts, (t_up, t_pan)
+
+    @staticmethod
+    def _pair_jobs(res, values, fallback, pool, n, C, itemsize, rice):
+        """The record of every pair of a coded block as a future of `pool` (the value field's zlib-9 runs there), None where fallback[f]
+        says the pair is not coded as an inter-frame.  res: GopCoder.results_packed(); values: per pair the changed values, or (rice)
+        the pair's sample stream.  The filter and the witness were built with the k rbf_plan_batch computed in C: the record carries
+        THAT value (the decoder derives floor_k and T from it), so a last-ulp difference to the Python twin is harmless."""
+        jobs = []
+        for f, r in enumerate(res):
+            if fallback[f]:
+                jobs.append(None)
+                continue
+            p = np.uint64(r["ones"]) / n
+            if r["l"]:
+                k = r["k"]
+                parts = (r["l"], r["filter"], r["witness_bits"], r["witness"])
+            else:                                # the reference passes the mask itself through (:215-225)
+                k, _l = P.optimal_params(n, p)
+                parts = (n, r["mask"], 0, b"")
+            vals = values[f]
+            if rice:
+                def job(p=p, k=k, parts=parts, stream=vals, count=r["ones"] * C):
+                    return struct.pack("<B", itemsize) + build_record("f64", p, n, k, *parts, count, stream)
+            else:
+                def job(p=p, k=k, parts=parts, vals=vals):
+                    vz = zlib.compress(vals, level=9)
+                    return struct.pack("<B", vals.dtype.itemsize) + build_record("f64", p, n, k, *parts, len(vals), vz)      # (VideoFrameCompressor's default wire format)
+            jobs.append(pool.submit(job))
+        return jobs
+
+    def _encode_block(self, seg, pool, run_starts=(), lane=None, busy=None):
+        """Inter-frame records of one block of consecutive frames in one pass over the GPU: seg[0] is only read (a keyframe, or a
+        shard's halo frame), every other frame is coded against its predecessor -- except the frames named in `run_starts` (indices
+        into seg), which are keyframes of the stream: they start a new run and the pair in front of them is not coded.  One upload,
+        ONE rbf_encode_runs launch sequence for all the runs, ONE exact-size download of the packed record (rbf_pack_records), one
+        batched gather of the changed values (luma mask: with the count of changes it cannot carry); zlib runs in `pool`.  With
+        frame_digests the block's frames are digested where they lie, after the hold (GopCoder.frame_digests): the result's `digests`.
+        With scene_cuts and pan_range the block is looked at right after its upload (_prepare_block): the result's `cuts`,
+        `pan_offsets` and `pans`.
+        lane: the context and coders to use (default: lane 0); busy: list that receives the (start, end) time of this block's GPU work.
+        Returns a _BlockRecords -- pairs: a future / None per pair (None = needs a keyframe, or is one) --, or None when the block
+        cannot be batched (_block_geometry)."""
+        t0 = time.perf_counter()
+        geometry = self._block_geometry(seg)
+        if isinstance(geometry, str):
+            return None
+        a, H, W, C, sb = geometry
+        if C > 4:                                # rbf_gather_values_batch carries at most 4 samples per pixel
+            return _BlockRecords([None] * (len(seg) - 1))
+        if lane is None:
+            lane = self._get_lanes(1)[0]
+        spec = self._coder_spec(a, len(seg))
+        coder = lane.coder(spec)
+        coder.set_run_starts(list(run_starts))
+        block = _as_block([frame_data(f) for f in seg])
+        tol = container.stat_tolerance(spec.max_error, None if spec.error_bounds is None else spec.error_bounds.min(), spec.hold_mode, sb)
+        t1 = time.perf_counter()
+        _, offsets, adopted, cuts, (t_up, t_pan) = self._prepare_block(coder, block, run_starts, tol)
         t2 = time.perf_counter()
         coder.encode()
         if self.profile_stages:
-            ctx.sync()
+            lane.ctx.sync()
         t3 = time.perf_counter()
         res = coder.results_packed()
         block_digests = coder.frame_digests() if self.frame_digests else None
         block_quality = coder.error_stats() if self.quality_report else None
         t4 = time.perf_counter()
         rice = self.sample_codec == "rice"
-        if mc == 1:
+        if spec.mask_channels == 1:
             values, uncovered = coder.gather_values(check_uncovered=True)
         else:
             values, uncovered = None if rice else coder.gather_values(check_uncovered=False), [0] * (len(seg) - 1)
@@ -521,47 +633,9 @@ class ImprovedVideoCompressor:
             self._tm_add(pan_align=t_pan - t_up)
         if busy is not None:
             busy.append((t1, t5))
-        n = H * W
-        out = _BlockRecords()
-        out.digests = block_digests
-        out.cuts = tuple(cuts)
-        out.quality = block_quality
-        out.pan_offsets, out.pans = offsets, adopted
-        panned = [False] * len(res)              # pair f belongs to a run that carries a non-zero offset
-        if offsets is not None:
-            bounds_of_runs = sorted({0} | {f + 1 for f, r in enumerate(res) if r.get("skipped")}) + [len(seg)]
-            for lo, hi in zip(bounds_of_runs, bounds_of_runs[1:]):
-                if any(offsets[t] != (0, 0) for t in range(lo, hi)):
-                    panned[lo:hi - 1] = [True] * (hi - 1 - lo)
-        broken = False                           # near-lossless: a frame of this run fell back to an (exact) keyframe
-        for f, r in enumerate(res):
-            if r.get("skipped"):                 # the pair in front of a keyframe
-                broken = False
-                out.append(None)
-                continue
-            if int(uncovered[f]) or broken:      # chroma moved where luma did not: not representable.  With max_error > 0 the rest of the run
-                broken = bool(self._near) or panned[f]       # goes with it: its records continue the HELD frames, not the exact keyframe the decoder will have (a panned run: the STABILISED frames)
-                out.append(None)
-                continue
-            p = np.uint64(r["ones"]) / n
-            if r["l"]:
-                # the filter and the witness were built with the k rbf_plan_batch computed in C: the record carries THAT
-                # value (the decoder derives floor_k and T from it), so a last-ulp difference to the Python twin is harmless
-                k = r["k"]
-                parts = (r["l"], r["filter"], r["witness_bits"], r["witness"])
-            else:                                # the reference passes the mask itself through (:215-225)
-                k, _l = P.optimal_params(n, p)
-                parts = (n, r["mask"], 0, b"")
-            vals = values[f]
-            if rice:
-                def job(p=p, k=k, parts=parts, stream=vals, count=r["ones"] * C):
-                    return struct.pack("<B", a.dtype.itemsize) + build_record("f64", p, n, k, *parts, count, stream)
-            else:
-                def job(p=p, k=k, parts=parts, vals=vals):
-                    vz = zlib.compress(vals, level=9)
-                    return struct.pack("<B", vals.dtype.itemsize) + build_record("f64", p, n, k, *parts, len(vals), vz)      # (VideoFrameCompressor's default wire format)
-            out.append(pool.submit(job))
-        return out
+        fallback = container.fallback_pairs([bool(r.get("skipped")) for r in res], uncovered, offsets, self._near)
+        return _BlockRecords(self._pair_jobs(res, values, fallback, pool, H * W, C, a.dtype.itemsize, rice),
+                             block_digests, cuts, offsets, adopted, block_quality)
 
     def encode_range(self, frames, first_index, start, stop, inter_frames=True, release=True):
         """[(type, record)] for the frames with global indices [start, stop); frames[i] is global frame
@@ -571,126 +645,44 @@ class ImprovedVideoCompressor:
         `gpu_lanes` contexts, each block on its own host thread; the host's zlib-9 (keyframes: four jobs each; changed values:
         one job per frame) runs on `num_threads` threads under all of it.  release: return the lanes' device memory as soon as the last
         block has left the GPU (False: keep the coders for the next call of the same geometry).
-        frame_digests=True: self.last_digests holds one digest per returned record (of the frame a decoder rebuilds from it), else None."""
-        records = {}
+        frame_digests=True: self.last_digests holds one digest per returned record (of the frame a decoder rebuilds from it), else None.
+        The keyframes the rule fixes in advance go to the host threads FIRST: their zlib-9 (the longest single jobs, ~0.2 s for a 1080p
+        frame, plus its three planes) then runs under the GPU's blocks instead of behind the last one."""
         I = self.keyframe_interval
-        inter_type = INTER_RICE if self.sample_codec == "rice" else INTER
         self.last_timing = tm = {}
         t_all = time.perf_counter()
         busy = []
-        gpu_keys = set()                         # sample_codec="rice": keyframes coded as type-3 records on the lanes
         fixed_keys, blocks = plan_range(first_index, start, stop, I, self.block_frames, inter_frames)
-        if self._near and blocks:
-            if self.error_bounds is not None and self.gop_batching:            # a bound frame that does not fit the clip: before any upload
+        if blocks:
+            if self._near and self.error_bounds is not None and self.gop_batching:     # a bound frame that does not fit the clip: before any upload
                 a = frame_data(frames[blocks[0][0] - first_index])
                 if a.dtype in (np.uint8, np.uint16) and a.ndim in (2, 3):
                     self._bound_frame(a)
-            off = blocks_off_keyframes(blocks, first_index, I)
-            if off:
-                raise ValueError("%s: the block that starts at frame %d does not start at a keyframe, so its held state would live in "
-                                 "another block's coder; make block_frames (%d) a multiple of keyframe_interval (%d) and start the range "
-                                 "on a keyframe" % ("max_error=%d" % self.max_error if self.max_error else "error_bounds", off[0][0], self.block_frames, I))
-        if self.pan_range and blocks and inter_frames:
-            off = blocks_off_keyframes(blocks, first_index, I)
-            if off:
-                raise ValueError("pan_range=%d: the block that starts at frame %d does not start at a keyframe, so its cumulative offset would "
-                                 "need the pairs in front of it; make block_frames (%d) a multiple of keyframe_interval (%d) and start the "
-                                 "range on a keyframe" % (self.pan_range, off[0][0], self.block_frames, I))
-        pans, pan_table = [], {}                 # pan_range: (frame, dx, dy) of the adopted pairs; frame -> its cumulative offset, if not (0, 0)
-        want = self.frame_digests
-        digests = {}                             # frame -> its digest, or the future of the host twin's
-        scene_cuts = []
-        quality = {}                             # quality_report: frame -> its row of the block it was coded in
+            check_blocks(self._options, blocks, first_index, I)
         in_block = {u for lo, end, _ in blocks for u in range(lo, end)} if self.gop_batching else set()
         with ThreadPoolExecutor(self.num_threads) as pool:
-            pending = {}
-
-            def digest_of(u, block_digests=None, j=0):
-                """Frame u's digest: entry j of its block's (taken on the GPU from the resident frames), else the host twin's of the caller's array."""
-                if not want or u in digests or not start <= u < stop:
-                    return
-                if block_digests is not None:
-                    digests[u] = int(block_digests[j])
-                else:
-                    digests[u] = pool.submit(frame_digest_host, frame_data(frames[u - first_index]))
-
-            def key(t):
-                if t in pending or t in gpu_keys:
-                    return
-                if self.sample_codec == "rice" and key_format(frames[t - first_index]) is not None:
-                    gpu_keys.add(t)
-                else:
-                    pending[t] = (KEY, self.compressor.compress_frame_jobs(frames[t - first_index], pool.submit))
+            book = _RangeRecords(self, frames, first_index, start, stop, pool)
 
             def run_block(block, take):
                 lo, end, starts = block
                 with take() as lane:
                     return self._encode_block(frames[lo - first_index:end - first_index], pool, starts, lane, busy)
-            # the keyframes the rule fixes in advance go to the host threads FIRST: their zlib-9 (the longest single jobs, ~0.2 s for a 1080p
-            # frame, plus its three planes) then runs under the GPU's blocks instead of behind the last one
             for t in fixed_keys:
-                key(t)
+                book.key(t)
                 if t not in in_block:            # (a keyframe inside a block is digested there, with the block's other frames)
-                    digest_of(t)
+                    book.digest_of(t)
             results = self._on_lanes(blocks, run_block) if self.gop_batching and blocks else [None] * len(blocks)
             tm["gpu_phase"] = time.perf_counter() - t_all                    # until the last block's values were on the host
             if release:                                                      # the lanes' blocks of frames, masks, filters and witnesses go back while the
                 t_rel = time.perf_counter()                                  # host threads still owe their zlib: not kept between videos
                 self._release_lanes()
                 tm["release"] = time.perf_counter() - t_rel
-            for (lo, end, starts), inter in zip(blocks, results):
-                seg = frames[lo - first_index:end - first_index]             # predecessor + the frames lo+1..end-1
-                # The block's digests describe its frames AFTER the hold.  The hold never writes a run's first frame (rbf_kernels_hold.h:
-                # "frame first[y] is never written"), so the block's first frame and the keyframes inside it -- the run starts handed to
-                # the coder -- still are the caller's originals, which is what their keyframe records code: their digests are taken
-                # from the block too.  Not so a frame that falls back to a keyframe with max_error > 0: its record codes the original,
-                # the block holds the held frame -- the host twin digests the original.
-                bd = getattr(inter, "digests", None)
-                cut = set(getattr(inter, "cuts", ()))                        # a cut frame is a run start of its block like a rule keyframe
-                scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
-                block_offsets = getattr(inter, "pan_offsets", None)
-                pans += [(lo + j, dx, dy) for j, dx, dy in getattr(inter, "pans", ()) if start <= lo + j < stop]
-                digest_of(lo, bd, 0)
-                for j in range(1, len(seg)):
-                    u = lo + j
-                    if is_keyframe(u, first_index, I) or j in cut:
-                        key(u)
-                        digest_of(u, bd, j)
-                        continue
-                    if inter is None:                                        # not batchable (or gop_batching=False): frame by frame
-                        digest_of(u)
-                        rec = self._encode_inter(seg[j - 1], seg[j])
-                        if rec is not None:
-                            records[u] = (inter_type, rec)
-                            continue
-                    elif inter[j - 1] is not None:
-                        pending[u] = (inter_type, inter[j - 1])
-                        digest_of(u, bd, j)
-                        if block_offsets is not None and block_offsets[j] != (0, 0) and start <= u < stop:
-                            pan_table[u - start] = block_offsets[j]
-                        if inter.quality is not None:
-                            quality[u] = inter.quality[j]
-                        continue
-                    key(u)
-                    digest_of(u, None if self._near else bd, j)
-            if gpu_keys:
-                t_key = time.perf_counter()
-                for u, rec in self._encode_keys_rice(frames, first_index, sorted(gpu_keys), busy).items():
-                    records[u] = (KEY_RICE, rec)
-                if release:
-                    self._release_lanes()
-                tm["gpu_phase"] += time.perf_counter() - t_key
-            t_wait = time.perf_counter()
-            for u, (ty, fut) in pending.items():
-                records[u] = (ty, fut() if ty == KEY else fut.result())
-            tm["zlib_wait"] = time.perf_counter() - t_wait                   # what the host threads' zlib-9 still owed after the last block left the GPU
-            self.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (digests[u] for u in range(start, stop))] if want else None
-        self.last_scene_cuts = sorted(scene_cuts)
-        self.last_pans, self.last_pan_offsets = sorted(pans), pan_table
-        self.last_quality = self._quality_dicts(frames, first_index, start, stop, quality) if self.quality_report else None
+            for block, inter in zip(blocks, results):
+                book.take_block(block, inter)
+            records = book.finish(release, tm, busy)
         _close_timing(tm, t_all, busy)
         tm["blocks"], tm["lanes"] = len(blocks), min(self.gpu_lanes, max(1, len(blocks)))
-        return [records[u] for u in range(start, stop)]
+        return records
 
     def _bound_frame(self, a):
         """(the bound frame of error_bounds for frames like `a`, d if all its entries equal d else None); kept, so that every block of a
@@ -787,11 +779,9 @@ class ImprovedVideoCompressor:
                    "keyframes": keyframes, "keyframe_ratio": keyframes / len(frames),
                    "output_path": output_path, "color_space": input_color_space, "overall_ratio": ratio}
         if self.max_error:
-            results["max_error"] = self.max_error
-            results["hold_mode"] = self.hold_mode
+            results.update(max_error=self.max_error, hold_mode=self.hold_mode)
         if self.error_bounds is not None:
-            results["error_bounds"] = True
-            results["hold_mode"] = self.hold_mode
+            results.update(error_bounds=True, hold_mode=self.hold_mode)
         if self.scene_cuts:
             results["scene_cuts"] = list(self.last_scene_cuts)
         if self.pan_range:
@@ -809,16 +799,10 @@ class ImprovedVideoCompressor:
     _parse_container = staticmethod(container.parse)
 
     # ------------------------------------------------------------------ decode
-    def decompress_video(self, input_path=None, output_path=None, compressed_frames=None, metadata=None, on_mismatch="raise"):
-        """The frames of a container (input_path) or of its records (compressed_frames).  A container with a digest trailer is checked
-        unless verify_digests=False: every inter-frame on the GPU, from the chain block it is rebuilt in; a type-3 keyframe on the GPU
-        where it is decoded; a type-1 keyframe by the host twin on the thread that inflated it.  The first frame, in stream order, whose
-        digest is not the stored one raises IntegrityError (on_mismatch="collect": no exception, self.last_bad_frames lists them all --
-        verify.verify_container).  self.last_integrity = {"frames", "checked", "device", "host"}."""
-        if on_mismatch not in ("raise", "collect"):
-            raise ValueError("on_mismatch must be 'raise' or 'collect', got %r" % (on_mismatch,))
-        start = time.time()
-        t_all = time.perf_counter()
+    @staticmethod
+    def _load_records(input_path, compressed_frames):
+        """(frame records, pan table, stored digests or None) of a container file or of a list of records, checked (container.split_tables,
+        check_types): a damaged trailer or pan table is a plain ValueError here, not a damaged frame."""
         records = None
         if input_path and os.path.exists(input_path):
             with open(input_path, "rb") as f:
@@ -827,102 +811,86 @@ class ImprovedVideoCompressor:
             records = [r if isinstance(r, tuple) else (KEY, r) for r in compressed_frames]
         if not records:
             raise ValueError("No compressed frames provided")
-        records, pan_table, stored = container.split_tables(records)         # (a damaged trailer or pan table is a plain ValueError here: not a damaged frame)
+        records, pan_table, stored = container.split_tables(records)
         if not records:
             raise ValueError("No compressed frames provided")
-        expected = stored if self.verify_digests else None
-        check = expected is not None
-        got = {}                                                             # record index -> (digest of the rebuilt frame, "device" | "host")
+        container.check_types([ty for ty, _ in records])
+        return records, pan_table, stored
+
+    def decompress_video(self, input_path=None, output_path=None, compressed_frames=None, metadata=None, on_mismatch="raise"):
+        """The frames of a container (input_path) or of its records (compressed_frames).  A container with a digest trailer is checked
+        unless verify_digests=False: every inter-frame on the GPU, from the chain block it is rebuilt in; a type-3 keyframe on the GPU
+        where it is decoded; a type-1 keyframe by the host twin on the thread that inflated it.  The first frame, in stream order, whose
+        digest is not the stored one raises IntegrityError (on_mismatch="collect": no exception, self.last_bad_frames lists them all --
+        verify.verify_container).  self.last_integrity = {"frames", "checked", "device", "host"}.
+        The keyframes are independent of everything else: they are inflated on the host threads while the inter-frame runs go through
+        the GPU (type-3 keyframes are decoded on the lanes: by the run that hangs off them, or by a job of their own).  Every run hangs
+        off its own keyframe, so the runs are independent too: they alternate over the lanes, each on its own host thread -- the inflate
+        and upload of run r+1 under the device-side rebuild and the download of run r."""
+        if on_mismatch not in ("raise", "collect"):
+            raise ValueError("on_mismatch must be 'raise' or 'collect', got %r" % (on_mismatch,))
+        start = time.time()
+        t_all = time.perf_counter()
+        records, pan_table, stored = self._load_records(input_path, compressed_frames)
+        log = _DigestLog(stored if self.verify_digests else None)
         types = [ty for ty, _ in records]
-        container.check_types(types)
         self.last_timing = tm = {}
         busy = []
-        # the keyframes are independent of everything else: inflate them on the host threads while the inter-frame runs go through the GPU
-        # (type-3 keyframes are decoded on the lanes: by the run that hangs off them, or by a job of their own)
         key_pool = ThreadPoolExecutor(self.num_threads)
+
         def key_job(rec):
             frame = self.compressor.decompress_frame(rec)
-            return frame, frame_digest_host(frame_data(frame)) if check else None
+            return frame, frame_digest_host(frame_data(frame)) if log.checking else None
         keys = {j: key_pool.submit(key_job, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
-        gkeys = {}
         runs = container.inter_runs(types)                                   # (index of the keyframe in front, first record, end)
-        decoded = {}
-
-        class dev_digest(list):
-            """A list that files what it receives as the device digests of the records first, first + 1, ..."""
-
-            def __init__(self, first, count):
-                super().__init__()
-                self.first = first
-
-            def extend(self, values):
-                for v in values:
-                    got[self.first + len(self)] = (int(v), "device")
-                    self.append(v)
-        if not check:
-            dev_digest = lambda first, count: None                          # noqa: E731
-
-        def host_digests(first, decoded_frames):
-            if check:
-                for i, f in enumerate(decoded_frames):
-                    got[first + i] = (frame_digest_host(frame_data(f)), "host")
-
-        def run_offsets(lo, hi):
-            """The cumulative pan offsets of the records lo .. hi-1, or None when none of them is rolled."""
-            offs = [pan_table.get(i, (0, 0)) for i in range(lo, hi)]
-            return offs if any(o != (0, 0) for o in offs) else None
+        gkeys, decoded = {}, {}                                              # type-3 keyframes a run's job decoded; first record of a run -> its frames
 
         def run_job(job, take):
             k, lo, hi = job
             base = keys[k].result()[0] if types[k] == KEY else None          # (waits for the host's inflate without holding a lane)
             with take() as lane:
                 if base is None:
-                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=dev_digest(k, 1))
+                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=log.sink(k))
                 if lo is None:
                     return None
                 return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi],
-                                        digests_out=dev_digest(lo, hi - lo), offsets=run_offsets(lo, hi))
+                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, hi))
         try:
             bases = {k for k, _, _ in runs}
             jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty == KEY_RICE and j not in bases]     # lone type-3 keyframes: no run
             if self.gop_batching and jobs:
-                # every run hangs off its own keyframe, so the runs are independent: they alternate over the lanes, each on its own host
-                # thread -- the inflate and upload of run r+1 under the device-side rebuild and the download of run r
                 for (_, lo, _), out in zip(jobs, self._on_lanes(jobs, run_job)):
                     if lo is not None:
                         decoded[lo] = out
             ends = {lo: hi for _, lo, hi in runs}
-            frames = []
-            i = 0
+            frames, i = [], 0
             while i < len(records):
                 if i not in ends:                                            # a keyframe
                     if types[i] == KEY:
                         frame, digest = keys[i].result()
                         frames.append(frame)
-                        if check:
-                            got[i] = (digest, "host")
+                        if log.checking:
+                            log.got[i] = (digest, "host")
                     else:
-                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=dev_digest(i, 1)))
+                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=log.sink(i)))
                     i += 1
                     continue
                 if i in decoded:
                     frames += decoded[i]
                 else:
                     stabilised = []
-                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]], run_offsets(i, ends[i]), stabilised)
-                    host_digests(i, stabilised)                              # (the digests describe the frames the records code)
+                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]], _run_offsets(pan_table, i, ends[i]), stabilised)
+                    log.host(i, stabilised)                                  # (the digests describe the frames the records code)
                 i = ends[i]
         finally:
             key_pool.shutdown(wait=True)
             self._release_lanes()
         _close_timing(tm, t_all, busy)
         tm["runs"], tm["lanes"] = len(runs), min(self.gpu_lanes, max(1, len(runs)))
-        self.last_integrity = {"frames": len(frames), "checked": len(got), "device": sum(1 for _, where in got.values() if where == "device"),
-                               "host": sum(1 for _, where in got.values() if where == "host")}
-        self.last_bad_frames = [i for i in sorted(got) if got[i][0] != expected[i]]
+        self.last_integrity, self.last_bad_frames = log.summary(len(frames))
         if self.last_bad_frames and on_mismatch == "raise":
             i = self.last_bad_frames[0]
-            raise IntegrityError(i, expected[i], got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEYS))
+            raise IntegrityError(i, log.expected[i], log.got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEYS))
         if output_path:
             self.save_frames_as_video(frames, output_path)
         if self.verbose:
@@ -1036,29 +1004,26 @@ class ImprovedVideoCompressor:
         if offsets is not None:
             container.check_pans({k: o for k, o in enumerate(offsets)}, base_arr.shape)
 
-        def unroll_from(i0):
-            """rebuild_chain's before_download hook for the stretch that starts at record i0 of the run."""
-            if offsets is None:
-                return None
-
-            def unroll(fb, c0, cnt):
-                offs = offsets[i0 + c0:i0 + c0 + cnt]
-                if not any(o != (0, 0) for o in offs):
-                    return False
-                L = nat.lib()
-                nat.check(L.rbf_memcpy_d2d(lane.ctx.handle, fb.ptr, fb.ptr + cnt * fbytes, fbytes))      # the next chunk's predecessor: still stabilised
-                neg = (nat._i32 * (2 * cnt))(*[-int(v) for o in offs for v in o])
-                nat.check(L.rbf_roll_frames(lane.ctx.handle, fb.ptr + fbytes, fbytes, cnt, W, H, pixel_bytes, neg))
-                return True
-            return unroll
+        def unroll(fb, c0, cnt):
+            """rebuild_chain's before_download hook: it runs inside the apply_chain calls below, where `i` is the record of the run the
+            stretch in hand starts at."""
+            offs = offsets[i + c0:i + c0 + cnt]
+            if not any(o != (0, 0) for o in offs):
+                return False
+            L = nat.lib()
+            nat.check(L.rbf_memcpy_d2d(lane.ctx.handle, fb.ptr, fb.ptr + cnt * fbytes, fbytes))          # the next chunk's predecessor: still stabilised
+            neg = (nat._i32 * (2 * cnt))(*[-int(v) for o in offs for v in o])
+            nat.check(L.rbf_roll_frames(lane.ctx.handle, fb.ptr + fbytes, fbytes, cnt, W, H, pixel_bytes, neg))
+            return True
+        before = None if offsets is None else unroll
         while i < len(parsed):                   # stretches of one record type: values written (type 2) or residuals added (type 4)
             j = i
             while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
                 j += 1
             if parsed[i]["rice"]:
-                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=unroll_from(i))
+                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before)
             else:
-                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=unroll_from(i))
+                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before)
             out += part
             prev, i = part[-1], j
             if offsets is not None and i < len(parsed) and offsets[i - 1] != (0, 0):      # the next stretch continues the stabilised frame

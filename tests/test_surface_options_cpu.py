@@ -1,0 +1,20 @@
+"""The constructor's outcome -- accepted, or which refusal wins -- over the whole keyword grid of surface_golden.py equals the recorded one
+(tests/golden/surface_refusals.json, written by tools/gen_surface_golden.py before surface_options.py existed)."""
+import itertools
+
+import surface_golden as sg
+from new_bloom_filter_repo_amd.video_compressor import ImprovedVideoCompressor
+
+
+def test_every_combination_of_the_grid_has_the_recorded_outcome():
+    want = sg.load(sg.REFUSALS)
+    assert want["grid"] == sg.grid_description() and want["dropped_values"] == []
+    outcomes, index = sg.refusal_table(ImprovedVideoCompressor)
+    assert len(index) == len(want["index"]) == 41472
+    if (outcomes, index) != (want["outcomes"], want["index"]):          # name the first combination that differs
+        names = [name for name, _ in sg.GRID]
+        for i, values in enumerate(itertools.product(*[v for _, v in sg.GRID])):
+            got, exp = outcomes[sg.SYMBOLS.index(index[i])], want["outcomes"][sg.SYMBOLS.index(want["index"][i])]
+            assert got == exp, (dict(zip(names, values)), got, exp)
+    assert outcomes == want["outcomes"] and index == want["index"] and len(outcomes) == 24
+    assert outcomes[0] == "ok" and index.count(sg.SYMBOLS[0]) == 136
