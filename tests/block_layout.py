@@ -5,7 +5,12 @@ LaneShape says which pixels of a frame the lane kernels' workgroups and the per-
 packed mask rows) out inside ONE large allocation so that every 64-bit byte offset a stage forms -- f * stride -- has a 32-bit truncation
 that lands on a DECOY inside the same allocation: an item of the same shape with other content, between two poisoned windows.  A kernel
 that truncates then reads or writes a decoy, the test sees a wrong answer or a changed decoy, and nothing outside the allocation is
-touched.  Only the items, decoys and windows are ever uploaded, filled or downloaded."""
+touched.  Only the items, decoys and windows are ever uploaded, filled or downloaded.
+
+Behind them: the inputs, references and conditions of the sweep's sibling (tests/test_gpu_block_stage_sweep_bounds_pan.py) -- the lane clips'
+bound frames and what a mis-addressed bound frame looks like, the planted maxima of the quality report, the pan clips with every candidate
+planted once, and the far cases with their decoys.  tests/test_block_stage_sweep_cpu.py asserts every condition on the CPU; the GPU tests
+assert them again in front of the device call."""
 import numpy as np
 
 WG_THREADS = 256            # csrc/rbf_device.h: the lane kernels' workgroup
@@ -197,3 +202,209 @@ def cut_non_vacuous(x, tolerance):
     moving = (np.abs(x[1:] - x[:-1]) > tolerance).any(axis=-1).reshape(len(x) - 1, -1)
     (lo, hi), (t0, t1) = shape.workgroup(2), shape.tail()
     return bool(moving[:, lo:hi].any() and not moving[:, lo:hi].all() and moving[:, t0:t1].any())
+
+
+# ------------------------------------------------------------------ the bound frame of the lane sweep (hold / look-ahead _map, quality report)
+MAP_RULES = ["hold", "lookahead"]
+ERR_LANE_PIXELS = 16                                             # csrc/rbf_kernels_error.h
+
+
+def rule_lane_pixels(rule):
+    return HOLD_LANE_PIXELS if rule == "hold" else LOOKAHEAD_LANE_PIXELS
+
+
+def lane_bounds(dtype, C):
+    """The bound frame of lane_clip(dtype, C): error_bounds_ref.test_bounds with seed C."""
+    from error_bounds_ref import test_bounds
+    return test_bounds((LANE_H, LANE_W, C), dtype, seed=C)[0]
+
+
+def map_ref(rule, x, starts, E):
+    from error_bounds_ref import hold_map_ref, lookahead_map_ref
+    return hold_map_ref(x, starts, E) if rule == "hold" else lookahead_map_ref(x, starts, E)[0]
+
+
+def swapped(x, f, d):
+    y = np.array(x)
+    y[f] = d
+    return y
+
+
+def aliased_bounds(E, lane_pixels):
+    """E as a kernel that mis-addresses the bound frame sees it: the third lane workgroup's pixels [lo, hi) carry the bounds of pixels
+    [0, hi - lo) -- what a load indexed by the lane's place in its workgroup brings -- and the five tail pixels those of pixels 0..4 --
+    what the per-pixel kernel reads if it drops its first pixel."""
+    shape = LaneShape(LANE_N, lane_pixels)
+    (lo, hi), (t0, t1) = shape.workgroup(2), shape.tail()
+    flat = np.array(E).reshape(LANE_N, -1)
+    out = flat.copy()
+    out[lo:hi] = flat[:hi - lo]
+    out[t0:t1] = flat[:t1 - t0]
+    return out.reshape(np.shape(E))
+
+
+def bounds_matter(x, want, rule, E):
+    """(pixel-frames of the third lane workgroup, pixel-frames of the tail) in which the reference of `rule` under aliased_bounds(E) differs
+    from `want`, its output under E.  Both above zero: a kernel that reads another pixel's bounds there writes another block."""
+    shape = LaneShape(LANE_N, rule_lane_pixels(rule))
+    ch = changed_pixels(want, map_ref(rule, x, LANE_STARTS, aliased_bounds(E, shape.lane_pixels)))
+    (lo, hi), (t0, t1) = shape.workgroup(2), shape.tail()
+    return int(ch[:, lo:hi].sum()), int(ch[:, t0:t1].sum())
+
+
+def stats_bounds(E):
+    """The three bounds the quality report of the sweep is taken against: the frame the block was held under (nothing is over it), half of
+    it and the scalar 0 (something is)."""
+    return [("frame", E), ("half", E // 2), ("zero", 0)]
+
+
+def region_stats(a, b, bounds, lo, hi):
+    """(sse, differing, over_bound) of error_stats_ref over the pixels [lo, hi) alone, summed over the frames."""
+    from error_bounds_ref import error_stats_ref
+    F = len(a)
+    cut = lambda v: np.asarray(v).reshape(F, LANE_N, -1)[:, lo:hi]
+    e = bounds if np.ndim(bounds) == 0 else np.asarray(bounds).reshape(LANE_N, -1)[lo:hi]
+    rows = error_stats_ref(cut(a), cut(b), e)
+    return int(rows["sse"].sum()), int(rows["differing"].sum()), int(rows["over_bound"].sum())
+
+
+def stats_regions():
+    """The pixels of the quality report's third lane workgroup and of its tail."""
+    shape = LaneShape(LANE_N, ERR_LANE_PIXELS)
+    return shape.workgroup(2), shape.tail()
+
+
+def plant_maxima(a, b):
+    """(a', b', places): copies in which one sample is 0 in a' and the top value in b' at each of places = [(frame, pixel, sample)]: frame 2
+    inside the tail, frame 4 in the last pixel of the third workgroup's last active lane, frame 5 in pixel 4095, the last of workgroup 0's
+    last lane.  A region that is dropped then shows in max_abs and not only in the sums."""
+    (lo, hi), (t0, t1) = stats_regions()
+    a, b = np.array(a), np.array(b)
+    F, C = len(a), a.shape[-1]
+    places = [(2, t0 + 2, 0), (4, hi - 1, C - 1), (5, WG_THREADS * ERR_LANE_PIXELS - 1, C - 1)]
+    fa, fb = a.reshape(F, LANE_N, C), b.reshape(F, LANE_N, C)
+    for f, p, c in places:
+        fa[f, p, c], fb[f, p, c] = 0, np.iinfo(a.dtype).max
+    return a, b, places
+
+
+def maxima_are_strict(a, b, places):
+    """Every planted sample is the one largest |a - b| of its frame."""
+    top = int(np.iinfo(a.dtype).max)
+    for f, p, c in places:
+        d = np.abs(a[f].astype(np.int64) - b[f].astype(np.int64)).reshape(LANE_N, -1)
+        if not (d[p, c] == top and int((d == top).sum()) == 1):
+            return False
+    return True
+
+
+# ------------------------------------------------------------------ pan search: every candidate of a range planted once
+PLANTED_RANGES = [1, 8, 9, 11, 14, 16, 17, 18, 21, 23, 25, 26, 28, 30, 32]
+
+
+def pan_chunk(R):
+    """csrc/rbf_kernels_pan.h: the consecutive dx a lane of k_pan_sad owns at range R."""
+    nd = 2 * R + 1
+    per_row = WG_THREADS // nd
+    return -(-nd // per_row)
+
+
+def planted_candidates(R, dtype=np.uint8, seed=1):
+    """(frames, shifts, tables): (2R+1)^2 + 1 random two-channel frames of (2R+9) x (2R+17) -- 3 x 2 grid points in one tile -- where frame f is
+    frame f-1 rolled by candidate f-1 = (dx, dy) in raster order (dy outer), so pair f-1's SAD is zero at that candidate; the pairs'
+    SAD tables from pan_ref.sad_tables."""
+    import pan_ref
+    rng = np.random.default_rng(seed)
+    H, W = 2 * R + 9, 2 * R + 17
+    shifts = [(dx, dy) for dy in range(-R, R + 1) for dx in range(-R, R + 1)]
+    frames = np.empty((len(shifts) + 1, H, W, 2), dtype=dtype)
+    frames[0] = rng.integers(0, int(np.iinfo(dtype).max) + 1, (H, W, 2))
+    for f, (dx, dy) in enumerate(shifts, start=1):
+        frames[f] = np.roll(frames[f - 1], (dy, dx), axis=(0, 1))
+    return frames, shifts, pan_ref.sad_tables(frames, R)
+
+
+def planted_zero_is_unique(shifts, tables, R):
+    """Every pair's table has exactly one zero, at its planted candidate: the pick has to find it, and a sum formed over another window, or
+    never stored, cannot stand in for it."""
+    zeros = tables == 0
+    s = np.array(shifts)
+    return bool((zeros.sum(axis=(1, 2)) == 1).all() and zeros[np.arange(len(s)), s[:, 1] + R, s[:, 0] + R].all())
+
+
+def planted_rows(frames, shifts, tables, R):
+    """The rows rbf_pan_search owes for planted_candidates: the planted shift, sad_best 0, sad_zero the table's centre, pan_ref's counts."""
+    import pan_ref
+    return [dict(dx=dx, dy=dy, sad_zero=int(tables[p, R, R]), sad_best=0, moving_zero=pan_ref.moving(frames[p], frames[p + 1], (0, 0)),
+                 moving_best=pan_ref.moving(frames[p], frames[p + 1], (dx, dy))) for p, (dx, dy) in enumerate(shifts)]
+
+
+# ------------------------------------------------------------------ the far cases of the bound-frame stages, the pan search and the roll
+FAR_MAP_CASES = [(np.uint8, 3), (np.uint16, 4)]
+FAR_MAP_IDS = ["u8c3", "u16c4"]
+FAR_STATS_BOUNDS = ["frame", 1]
+FAR_PAN = (320, 180, 8)                                          # W, H, R: 3 x 3 tiles
+FAR_ROLLS = [(64, 16, 4), (67, 33, 3)]                           # W, H, pixel bytes: the vector path | the byte path
+FAR_ROLL_IDS = ["64x16_pb4_vectors", "67x33_pb3_bytes"]
+
+
+def far_clip(seed, dtype, C):
+    from near_lossless_ref import random_clip
+    return random_clip(seed, 3, LANE_H, LANE_W, C, dtype)
+
+
+def far_map_case(rule, dtype, C):
+    """(x, decoys, E, want): one run of three 799x11 frames, the decoys of frames 1 and 2, the bound frame, the reference's block."""
+    x, decoys, E = far_clip(8110 + C, dtype, C), list(far_clip(8210 + C, dtype, C)[1:]), lane_bounds(dtype, C)
+    return x, decoys, E, map_ref(rule, x, [], E)
+
+
+def far_map_decoys_matter(rule, x, decoys, E, want):
+    return not np.array_equal(want, x) and all(not np.array_equal(map_ref(rule, swapped(x, f, decoys[f - 1]), [], E)[f], want[f]) for f in (1, 2))
+
+
+def far_stats_case(dtype, C):
+    """(a, b, E, a_decoys, b_decoys): originals, the block held under E, and decoys for the far frames of either."""
+    a, E = far_clip(8310 + C, dtype, C), lane_bounds(dtype, C)
+    return a, map_ref("hold", a, [], E), E, list(far_clip(8410 + C, dtype, C)[1:]), list(far_clip(8510 + C, dtype, C)[1:])
+
+
+def far_stats_decoys_matter(a, b, bounds, a_decoys, b_decoys):
+    """Row f of the report changes when frame f of A, or of B, is its decoy."""
+    from error_bounds_ref import error_stats_ref
+    want = error_stats_ref(a, b, bounds)
+    return all(error_stats_ref(swapped(a, f, a_decoys[f - 1]), b, bounds)[f] != want[f] and
+               error_stats_ref(a, swapped(b, f, b_decoys[f - 1]), bounds)[f] != want[f] for f in (1, 2))
+
+
+def far_pan_case():
+    """(frames, decoys, rows): three 320x180 8-bit frames of pan_ref's panning camera, decoys from another scene, pan_ref.stat_rows."""
+    import pan_ref
+    W, H, R = FAR_PAN
+    x = np.stack(pan_ref.planted_clip(W, H, R, np.uint8, nframes=3)[0])
+    decoys = pan_ref.planted_clip(W, H, R, np.uint8, seed=6, nframes=3)[0][1:]
+    return x, decoys, pan_ref.stat_rows(x, R, 0)
+
+
+def far_pan_decoys_matter(x, decoys, rows):
+    """A decoy in place of frame 1 changes both rows, one in place of frame 2 the second."""
+    import pan_ref
+    R = FAR_PAN[2]
+    one, two = pan_ref.stat_rows(swapped(x, 1, decoys[0]), R, 0), pan_ref.stat_rows(swapped(x, 2, decoys[1]), R, 0)
+    return one[0] != rows[0] and one[1] != rows[1] and two[1] != rows[1]
+
+
+def far_roll_case(W, H, pb):
+    """(x, decoys, offsets, want): three frames of H x W pixels of pb bytes, every one rolled."""
+    import pan_ref
+    rng = np.random.default_rng(100 * W + pb)
+    x = rng.integers(0, 256, (3, H, W, pb), dtype=np.uint8)
+    decoys = list(rng.integers(0, 256, (2, H, W, pb), dtype=np.uint8))
+    offsets = [(5, -7), (W - 1, 1), (3, 0)]
+    return x, decoys, offsets, np.stack([pan_ref.roll(f, ox, oy) for f, (ox, oy) in zip(x, offsets)])
+
+
+def far_roll_decoys_matter(x, decoys, offsets, want):
+    import pan_ref
+    return all(not np.array_equal(want[f], x[f]) for f in range(3)) and \
+        all(not np.array_equal(pan_ref.roll(decoys[f - 1], *offsets[f]), want[f]) for f in (1, 2))

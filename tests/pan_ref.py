@@ -29,6 +29,21 @@ def sad_table(prev, cur, R):
     return {(dx, dy): int(np.abs(Yc[np.ix_(ys + dy, xs + dx)] - ref).sum()) for dy in range(-R, R + 1) for dx in range(-R, R + 1)}
 
 
+def sad_tables(frames, R):
+    """The SAD tables of every pair of `frames` at once, int64 (pairs, 2R+1, 2R+1) indexed [pair, dy + R, dx + R]: for every grid point the
+    window Yc[y-R:y+R+1, x-R:x+R+1] against Yp[y, x].  sad_table walks the candidates in Python, too slow for the thousands of pairs of
+    a clip with every candidate of R = 32 planted; test_block_layout_cpu.py proves the two equal."""
+    Y = np.stack([luma(f) for f in frames])
+    H, W = Y.shape[1:]
+    xs, ys = grid_points(W, H, R)
+    out = np.zeros((len(Y) - 1, 2 * R + 1, 2 * R + 1), dtype=np.int64)
+    Y = Y.astype(np.int16 if Y.max(initial=0) < 1 << 15 else np.int32)   # (the narrowest type the differences fit: this is memory-bound)
+    for y in ys:
+        for x in xs:
+            out += np.abs(Y[1:, y - R:y + R + 1, x - R:x + R + 1] - Y[:-1, y, x][:, None, None])
+    return out
+
+
 def pick(table):
     """The candidate with the smallest (SAD, |dx|+|dy|, |dy|, dy, dx)."""
     return min(table, key=lambda v: (table[v], abs(v[0]) + abs(v[1]), abs(v[1]), v[1], v[0]))
@@ -142,6 +157,8 @@ def planted_clip(width=96, height=64, R=4, dtype=np.uint8, sensor_noise=0, seed=
     assert got == shifts
     if channels == 1:
         frames = [np.ascontiguousarray(f[..., 0]) for f in frames]
+    elif channels == 2:
+        frames = [np.ascontiguousarray(f[..., :2]) for f in frames]
     elif channels == 4:
         frames = [np.ascontiguousarray(np.concatenate([f, f[..., :1] ^ 0x55], axis=2)) for f in frames]
     return frames, shifts

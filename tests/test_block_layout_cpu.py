@@ -8,8 +8,10 @@ import block_layout as bl
 from lookahead_ref import lookahead_ref
 from near_lossless_ref import hold_ref
 
-# (item bytes) of every far case of the sweep: 799x11 and 128x64 frames of u8 C=3, u16 C=4, u16 C=1, planar u8 luma; 70 000 digest bytes
-FRAME_BYTES = [799 * 11 * 3, 799 * 11 * 8, 799 * 11 * 2, 799 * 11, 128 * 64 * 3, 128 * 64, 70000, bl.ITEM_MAX]
+# (item bytes) of every far case of the sweep: 799x11 and 128x64 frames of u8 C=3, u16 C=4, u16 C=1, planar u8 luma; 70 000 digest bytes;
+# the pan search's 320x180 u8 C=3 frames; the roll's 64x16 pixels of 4 bytes and 67x33 pixels of 3 bytes
+FRAME_BYTES = [799 * 11 * 3, 799 * 11 * 8, 799 * 11 * 2, 799 * 11, 128 * 64 * 3, 128 * 64, 70000, 320 * 180 * 3, 64 * 16 * 4, 67 * 33 * 3,
+               bl.ITEM_MAX]
 ROW_BYTES = [(799 * 11 + 63) // 64 * 8, 128 * 64 // 8, bl.ROW_MAX]
 
 

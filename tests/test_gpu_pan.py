@@ -68,7 +68,7 @@ def search(ctx, frames, R, tolerance=0, run_starts=None, pad=0, **override):
 SHAPES = [(96, 64, 4), (67, 33, 4), (50, 40, 16), (80, 72, 32), (320, 180, 8)]
 
 
-@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("C", [1, 2, 3, 4])
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d_R%d" % s)
 def test_search_equals_the_reference(ctx, shape, dtype, C):
