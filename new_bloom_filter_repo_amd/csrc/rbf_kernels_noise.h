@@ -8,6 +8,7 @@
 // property of numpy's pairwise summation, not of the data.
 #pragma once
 #include "rbf_device.h"
+#include "rbf_median_net.h"
 
 namespace rbf {
 
@@ -16,28 +17,7 @@ constexpr int NZ_LDS_W = NZ_TILE_W + 4, NZ_LDS_H = NZ_TILE_H + 4;
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-// Batcher's odd-even merge sort on 32 wires, restricted to the 25 wires that carry data (the other
-// seven would hold +inf and never move).  Only wire 12 -- the median -- is consumed, so the compiler
-// drops every min/max that cannot reach it (202 packed min/max remain out of 280).
-struct MedianNet {
-    int n;
-    unsigned char a[192], b[192];
-};
-constexpr MedianNet make_median_net()
-{
-    MedianNet net{};
-    for (int p = 1; p < 32; p <<= 1)
-        for (int k = p; k >= 1; k >>= 1)
-            for (int j = k % p; j + k < 32; j += 2 * k)
-                for (int i = 0; i < (k < 32 - j - k ? k : 32 - j - k); ++i)
-                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p) && i + j + k < 25) {
-                        net.a[net.n] = (unsigned char)(i + j);
-                        net.b[net.n] = (unsigned char)(i + j + k);
-                        ++net.n;
-                    }
-    return net;
-}
-
+// (MedianNet / make_median_net: rbf_median_net.h -- the comparator list, proven over every input by tests/c/median_net_cases.cpp)
 __device__ __forceinline__ u16x2 median25(u16x2 (&v)[25])
 {
     constexpr MedianNet net = make_median_net();
