@@ -503,6 +503,34 @@ int rbf_rice_apply_inter(rbf_ctx *ctx, const void *streams, const uint64_t *stre
                          uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                          const void *masks_dev, uint64_t mask_stride_bytes, void *frames_dev);
 
+/* ---- bounded-error keyframes: the quantiser inside the keyframe predictor (no reference counterpart) ---------- */
+/* A keyframe within a bound per channel instead of exact (record type 7 of 'BFV2' containers: the type-3 head '<IIIBB' height, width,
+ * itemsize, channels, yuv | '<B' version = 1 | '<B' n = max(1, channels) | n x '<H' d_c | zero padding to 4 bytes | a sample stream of
+ * height * width * n samples).  THE RULE (normative).  Frame X is (H, W, C) with B-bit samples, channel c has bound d_c and step
+ * t_c = 2 d_c + 1, S is an integer state per sample, the order is raster order:
+ *     P(y, x, c) = S(y, x-1, c) for x > 0;  P(y, 0, c) = S(y-1, 0, c) for y > 0;  P(0, 0, c) = 0      (the type-3 neighbours)
+ *     d_c >= 1:  e = X - P;  q = sgn(e) * floor((|e| + d_c) / t_c);  S = P + q t_c;  Y = clamp(S, 0, 2^B - 1)
+ *     d_c == 0:  q = (X - P) mod 2^B read as B-bit two's complement;  S = X;  Y = X                    (the type-3 rule)
+ *     stream sample u = 2q for q >= 0, -2q - 1 otherwise
+ * So |X - Y| <= |X - S| <= d_c, S stays in [-d_c, 2^B - 1 + d_c], |q| <= (2^B + 1) / 3 and u < 2^B.  The stream is an unchanged sample
+ * stream: N = H W C, chunks of 1024, the same rule for k, channels interleaved.  A decoder sums q t_c down column 0 and along every row
+ * (32-bit wrap-around arithmetic is exact: every true partial sum is in range), then Y = clamp(sum) where d_c >= 1 and sum mod 2^B where
+ * d_c == 0.  Y is a pure function of (X, d): two blocks that hold the same keyframe get the same Y.  The loop has a closed form: it
+ * starts at 0 and moves in multiples of t_c, so S = t_c * floor((X + d_c) / t_c) whatever the neighbours are -- S is never negative, the
+ * upper clamp binds where a multiple of t_c lies just above 2^B - 1, and quantising Y again gives Y.
+ *   the encode entry  quantises the `count` frames frame_index[0] < frame_index[1] < ... (host; frame i of the block lies at frames_dev +
+ *                     i * frame_stride_bytes, dense as above; an index is < 65535) IN PLACE -- each becomes its Y -- and writes their
+ *                     streams back to back at out_dev; stream_bytes (host, count) receives their sizes, capacity_bytes as for
+ *                     rbf_rice_encode_intra.  No other frame of the block is touched.  Blocks.
+ *   the decode entry  one stream (HOST memory) back into the dense frame Y at frame_dev, as rbf_rice_decode_intra does for type 3.
+ * bounds: `channels` host entries, each <= 65535.  Arguments, capacities and stream headers are checked before anything is launched:
+ * RBF_EINVAL with rbf_last_error(), and a refused call writes neither frames nor output.  Not timed: there is no RBF_K_ id for them. */
+int rbf_rice_encode_intra_near(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, const uint32_t *frame_index, uint32_t count,
+                               uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes, const uint32_t *bounds,
+                               void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes);
+int rbf_rice_decode_intra_near(rbf_ctx *ctx, const void *stream, uint64_t stream_bytes, uint32_t width, uint32_t height,
+                               uint32_t channels, uint32_t sample_bytes, const uint32_t *bounds, void *frame_dev);
+
 /* ---- integrity: frame digests (no reference counterpart) ------------------------------------------ */
 /* FD1, the digest a container stores per frame so that a decoder can prove, without the originals, that it rebuilt the frames the
  * encoder coded (record type 5 of 'BFV2' containers: '<B' version = 1 | '<B' algo = 1 | '<H' 0 | '<I' count | count x '<Q' digest |

@@ -105,6 +105,9 @@ _PROTOS = {
     "rbf_rice_encode_inter": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64,
                                      ctypes.POINTER(_u64)]),
     "rbf_rice_apply_inter": (_int, [_vp, _vp, ctypes.POINTER(_u64), _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "rbf_rice_encode_intra_near": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u32), _u32, _u32, _u32, _u32, _u32, ctypes.POINTER(_u32), _vp, _u64,
+                                          ctypes.POINTER(_u64)]),
+    "rbf_rice_decode_intra_near": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, ctypes.POINTER(_u32), _vp]),
     "rbf_cut_stats": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_error_stats": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
     "rbf_pan_search": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),

@@ -10,6 +10,8 @@ every record with a type byte, following the type-byte precedent of VideoFrameCo
       frame: split_trailer takes it off, and everything else in this module sees the frame records only.
   6 = the pan table (build_pans has the layout): optional, behind the last frame record and in front of a digest trailer.  It is no frame
       either: split_tables takes it off.
+  7 = a keyframe within a bound per channel (bounded_keyframes=True; sample_codec.py has its layout).  KEYS stays the pair of exact
+      keyframe types; KEY_TYPES names every keyframe type, and is what the stream checks below go by.
 """
 import struct
 
@@ -18,6 +20,8 @@ KEYS, INTERS = (KEY, KEY_RICE), (INTER, INTER_RICE)
 DIGESTS = 5
 PANS = 6
 PANS_VERSION = 1
+KEY_NEAR = 7
+KEY_TYPES = KEYS + (KEY_NEAR,)
 
 
 def write(records):
@@ -215,7 +219,7 @@ def split_trailer(records):
 def check_types(types):
     """ValueError unless every type is known and the stream starts with a keyframe."""
     for ty in types:
-        if ty not in KEYS + INTERS:
+        if ty not in KEY_TYPES + INTERS:
             raise ValueError(f"unknown record type {ty}")
     if types and types[0] in INTERS:
         raise ValueError("inter-frame without a preceding keyframe")
@@ -225,7 +229,7 @@ def inter_runs(types):
     """The maximal runs of inter-frame records of a checked stream: [(index of the keyframe in front, first record, end)]."""
     runs, i = [], 0
     while i < len(types):
-        if types[i] in KEYS:
+        if types[i] in KEY_TYPES:
             i += 1
             continue
         j = i

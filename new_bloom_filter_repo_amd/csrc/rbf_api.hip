@@ -22,6 +22,7 @@
 #include "rbf_kernels_error.h"
 #include "rbf_kernels_pan.h"
 #include "rbf_rice_host.h"
+#include "rbf_kernels_keyquant.h"
 
 #include <cmath>
 #include <cstring>
@@ -1514,6 +1515,90 @@ int rbf_rice_decode_intra(rbf_ctx *ctx, const void *stream, uint64_t stream_byte
         using S = decltype(s);
         hipLaunchKernelGGL(k_rice_intra_rebuild<S>, dim3((height + WG_WAVES - 1) / WG_WAVES), dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u.p, width,
                            height, channels, (uint32_t)(8 * sizeof s), (S *)frame_dev);
+    });
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
+}
+
+// ---- bounded-error keyframes (rbf_kernels_keyquant.h)
+// The per-channel table of a call: bounds (host, `channels` entries, each <= 65535) -> bound, step and the step's reciprocal.
+static int keyquant_table(const uint32_t *bounds, uint32_t channels, KeyQuant *kq)
+{
+    *kq = KeyQuant{};
+    for (uint32_t c = 0; c < 4; ++c) {
+        const uint32_t d = c < channels ? bounds[c] : 0;
+        if (d > 65535) return fail(RBF_EINVAL, "bound %u of channel %u: a bound is at most 65535", d, c);
+        const uint32_t t = 2 * d + 1;
+        kq->d[c] = d; kq->t[c] = t;
+        if (d) {
+            uint32_t L = 0;
+            while ((t >> (L + 1)) != 0) ++L;                       // floor(log2 t) >= 1
+            const uint64_t K = 31 + L;
+            kq->m[c] = (uint32_t)((((uint64_t)1 << K) + t - 1) / t);
+            kq->sh[c] = L - 1;
+        }
+    }
+    return RBF_OK;
+}
+
+int rbf_rice_encode_intra_near(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, const uint32_t *frame_index, uint32_t count,
+                               uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes, const uint32_t *bounds,
+                               void *out_dev, uint64_t capacity_bytes, uint64_t *stream_bytes)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!frames_dev || !frame_index || !bounds || !out_dev || !stream_bytes) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    if (count == 0 || count > 65535) return fail(RBF_EINVAL, "count must be 1..65535, got %u", count);
+    for (uint32_t i = 0; i < count; ++i) {
+        if (frame_index[i] >= 65535) return fail(RBF_EINVAL, "frame index %u: a block holds at most 65535 frames", frame_index[i]);
+        if (i && frame_index[i] <= frame_index[i - 1])           // (a frame listed twice would have two streams)
+            return fail(RBF_EINVAL, "frame indices must ascend: %u after %u", frame_index[i], frame_index[i - 1]);
+    }
+    const uint64_t n = (uint64_t)width * height * channels;
+    if (int r = rice_check_dense(frame_stride_bytes, n, sample_bytes)) return r;
+    KeyQuant kq;
+    if (int r = keyquant_table(bounds, channels, &kq)) return r;
+    RicePlan p;
+    std::vector<uint64_t> ns;
+    try { ns.assign(count, n); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); }
+    if (int r = rice_plan(ns.data(), count, 8 * sample_bytes, capacity_bytes, &p)) return r;
+    if (int r = rice_stage(ctx, p)) return r;
+    if (int r = ctx->keyq.reserve((size_t)count * 4)) return r;
+    HIP_TRY(hipMemcpyAsync(ctx->keyq.p, frame_index, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));      // (pageable: staged before the call returns)
+    const dim3 grid((uint32_t)(((uint64_t)width * channels + WG_THREADS - 1) / WG_THREADS), height, count);
+    int rc = RBF_OK;
+    by_sample_width(sample_bytes, [&](auto s) {
+        using S = decltype(s);
+        constexpr uint32_t B = 8 * sizeof s;
+        hipLaunchKernelGGL(k_keyquant_u<S>, grid, dim3(WG_THREADS), 0, ctx->stream, (const uint8_t *)frames_dev, frame_stride_bytes, ctx->keyq.p,
+                           width, channels, kq, ctx->rice_u.p);
+        hipLaunchKernelGGL(k_keyquant_apply<S>, grid, dim3(WG_THREADS), 0, ctx->stream, (uint8_t *)frames_dev, frame_stride_bytes, ctx->keyq.p,
+                           width, channels, kq);
+        rc = rice_encode_streams<B>(ctx, p, out_dev, stream_bytes);
+    });
+    return rc;
+}
+
+int rbf_rice_decode_intra_near(rbf_ctx *ctx, const void *stream, uint64_t stream_bytes, uint32_t width, uint32_t height,
+                               uint32_t channels, uint32_t sample_bytes, const uint32_t *bounds, void *frame_dev)
+{
+    if (int r = set_device(ctx)) return r;
+    if (!stream || !bounds || !frame_dev) return fail(RBF_EINVAL, "null pointer");
+    if (int r = rice_check_frame(width, height, channels, sample_bytes)) return r;
+    KeyQuant kq;
+    if (int r = keyquant_table(bounds, channels, &kq)) return r;
+    const uint64_t want = (uint64_t)width * height * channels;
+    std::vector<RiceChunk> ch;
+    uint64_t n = 0;
+    if (int r = rice_parse((const uint8_t *)stream, stream_bytes, 0, 8 * sample_bytes, 0, 0, &ch, &n)) return r;
+    if (n != want)
+        return fail(RBF_EINVAL, "the stream carries %llu samples, a %ux%ux%u frame has %llu", (unsigned long long)n, width, height, channels,
+                    (unsigned long long)want);
+    if (int r = rice_decode(ctx, stream, stream_bytes, ch, n)) return r;
+    by_sample_width(sample_bytes, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL(k_keyquant_rebuild<S>, dim3((height + WG_WAVES - 1) / WG_WAVES), dim3(WG_THREADS), 0, ctx->stream, ctx->rice_u.p, width,
+                           height, channels, kq, (S *)frame_dev);
     });
     HIP_TRY(hipGetLastError());
     return RBF_OK;

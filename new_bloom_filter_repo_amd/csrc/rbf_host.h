@@ -110,6 +110,7 @@ struct rbf_ctx {
     DevBuf<void> rice_tab;           // the call's stream / chunk table
     DevBuf<void> rice_blob;          // uploaded streams (decode)
     DevBuf<uint32_t> rice_err;       // decode / apply error flag
+    DevBuf<uint32_t> keyq;           // bounded-error keyframes (rbf_kernels_keyquant.h): the call's frame indices
     DevBuf<uint8_t> hold_bits;       // look-ahead hold (rbf_kernels_lookahead.h): the segment-start bits, nframes rows of ceil(n / 8) bytes
     DevBuf<uint64_t> digest_lvl;     // frame digests (rbf_kernels_digest.h): the block hashes of every level, per frame of the call
     DevBuf<uint32_t> cut_partials;   // scene-cut statistics (rbf_kernels_cut.h): three sums per wave and pair of the call

@@ -137,6 +137,7 @@ class GopCoder:
             raise ValueError("hold_mode='lookahead' is a near-lossless stage: it needs max_error > 0 or error_bounds")
         self.hold_mode = hold_mode
         self._held = set()                            # look-ahead: the resident GOPs that already are their held sequence
+        self._key_streams = {}                        # bounded keyframes: resident GOP -> what quantise_run_starts() made of it
         self.ctx, self.W, self.H, self.F, self.C, self.sb = ctx, width, height, nframes, channels, sample_bytes
         self.n = width * height
         self.pairs = nframes - 1
@@ -254,6 +255,7 @@ class GopCoder:
         """Slot `gop` holds new input frames (load_frames() calls this; a caller that fills the block some other way does): the next
         encode() of it runs the look-ahead hold again."""
         self._held.discard(gop)
+        self._key_streams.pop(gop, None)
 
     def load_luma(self, planes, gop=0):
         """Upload one GOP of dense (F, H, W) Y planes (planar_luma coders)."""
@@ -287,6 +289,46 @@ class GopCoder:
                 lo = threshold_floor(adaptive_threshold(np.std(plane), *self.adaptive))
             floors.append(lo)
         return floors
+
+    def key_bounds(self):
+        """The per-channel bounds of the coder's near-lossless stage: max_error for every channel, or the channels' entries of a bound
+        frame that is the same at every pixel.  ValueError for a lossless coder and for bounds that differ from pixel to pixel (a
+        decoder of a bounded keyframe would need the map, which its record does not carry)."""
+        if self.error_bounds is None:
+            d = [self.max_error] * self.C
+        else:
+            e = self.error_bounds.reshape(-1, self.C)
+            if not bool((e == e[0]).all()):
+                raise ValueError("bounded keyframes carry one bound per channel: not with error_bounds that differ from pixel to pixel")
+            d = [int(v) for v in e[0]]
+        if not any(d):
+            raise ValueError("bounded keyframes are a near-lossless stage: they need max_error > 0 or error_bounds")
+        return d
+
+    def quantise_run_starts(self, sample_coder, frames=None, gop=0):
+        """Bounded-error keyframes: quantise the run firsts of resident GOP `gop` IN PLACE within key_bounds() and return {j: the type-7
+        sample stream of frame j} (SampleCoder.encode_near: rbf_rice_encode_intra_near, one launch sequence and one exact-size download).
+        frames: the block indices to quantise (default: frame 0 and every run start); each has to be a run first -- the hold never
+        writes those, so what encode() and everything behind it see of them is Y, and the inter-frames that hang off them are held
+        against Y.  Call it after load_frames() (and align_pans / set_run_starts), before encode().  The stage runs ONCE PER
+        load_frames(): a second call returns the first call's streams and launches nothing (Y is a fixed point of the rule, so a
+        second pass would only repeat the work)."""
+        if self.planar_luma or self.frames is None:
+            raise ValueError("the keyframe quantiser rewrites the interleaved frames: not with planar_luma")
+        assert 0 <= gop < self.resident_gops
+        if gop in self._key_streams:
+            return self._key_streams[gop]
+        firsts = [0] + [t for t in range(1, self.F) if self.run_starts is not None and self.run_starts[t]]
+        idx = firsts if frames is None else sorted({int(j) for j in frames})
+        if any(j not in firsts for j in idx):
+            raise ValueError("frames %r: only run firsts (%r) can be bounded keyframes" % (idx, firsts))
+        out = {}
+        if idx:
+            streams = sample_coder.encode_near(self._block_ptr(self.frames, gop), self.frame_bytes, self.F, idx, self.W, self.H, self.C, self.sb,
+                                               self.key_bounds())
+            out = dict(zip(idx, streams))
+        self._key_streams[gop] = out
+        return out
 
     def encode(self, gop=0):
         """Enqueue one full pass over resident GOP `gop`; returns after the Bloom kernels are enqueued."""

@@ -13,6 +13,8 @@ Records of 'BFV2' containers (next to type 1 = zlib keyframe, 2 = inter-frame):
                    H*W*C samples, predicted from the pixel to the left (column 0: the pixel above; the first pixel: 0), per channel
   4 = inter-frame  type 2's bytes ('<B' itemsize + the "f64" wire record) with the stream of the pair's residuals against frame t-1 at the
                    mask's pixels in the value field; value_count = its sample count
+  7 = keyframe     within a bound per channel (bounded_keyframes=True; include/rbf.h has the rule): type 3's head | '<B' version = 1 |
+                   '<B' n = max(1, channels) | n x '<H' d_c | zero padding to 4 bytes | the stream of the quantised residuals q
 """
 import ctypes
 import struct
@@ -20,13 +22,14 @@ import struct
 import numpy as np
 
 from . import _native as nat
-from .container import INTER_RICE, KEY_RICE  # noqa: F401  (the record types this module's streams travel in)
+from .container import INTER_RICE, KEY_NEAR, KEY_RICE  # noqa: F401  (the record types this module's streams travel in)
 from .engine import rebuild_chain
 from .frame_codec import YUVFrame, _PlaneDict, frame_data
 
 CHUNK = 1024
 _KEY_HEAD = struct.Struct("<IIIBB")
 _PLANES = ("y_plane", "u_plane", "v_plane")
+NEAR_VERSION = 1
 
 
 def nchunks(n):
@@ -102,6 +105,51 @@ def parse_key_record(rec):
     return {"height": h, "width": w, "itemsize": item, "channels": channels, "yuv": yuv, "stream": stream}
 
 
+def _near_bounds(bounds, n):
+    d = [int(v) for v in bounds]
+    if len(d) != n or any(not 0 <= v <= 65535 for v in d):
+        raise ValueError("a type-7 record carries %d bounds in 0..65535, got %r" % (n, list(bounds)))
+    return d
+
+
+def near_key_record(frame, bounds, stream):
+    """The type-7 record of `frame` -- only its shape, dtype and yuv_info are read -- around the stream rbf_rice_encode_intra_near made of
+    it under the per-channel `bounds`."""
+    arr = frame_data(frame)
+    channels, yuv = key_format(frame)
+    n = max(1, channels)
+    head = _KEY_HEAD.pack(arr.shape[0], arr.shape[1], arr.dtype.itemsize, channels, yuv) + struct.pack("<BB%dH" % n, NEAR_VERSION, n, *_near_bounds(bounds, n))
+    return head + b"\0" * (-len(head) % 4) + bytes(stream)
+
+
+def parse_near_key_record(rec):
+    """Fields of a type-7 record (parse_key_record's, and `bounds`: the n per-channel bounds); ValueError for a version other than 1, an n
+    other than max(1, channels), non-zero padding, or a stream whose N or B disagrees with the head."""
+    if len(rec) < _KEY_HEAD.size + 2:
+        raise ValueError("truncated bounded keyframe record")
+    h, w, item, channels, yuv = _KEY_HEAD.unpack_from(rec, 0)
+    if item not in (1, 2) or channels > 4 or yuv > 1 or h == 0 or w == 0:
+        raise ValueError("bounded keyframe record: itemsize %d, %d channels, yuv %d" % (item, channels, yuv))
+    version, n = struct.unpack_from("<BB", rec, _KEY_HEAD.size)
+    if version != NEAR_VERSION:
+        raise ValueError("bounded keyframe record version %d is unknown (this reader knows %d)" % (version, NEAR_VERSION))
+    if n != max(1, channels):
+        raise ValueError("bounded keyframe record: %d bounds for %d channel(s)" % (n, max(1, channels)))
+    off = _KEY_HEAD.size + 2 + 2 * n
+    body = off + (-off % 4)
+    if len(rec) < body + 8:
+        raise ValueError("truncated bounded keyframe record")
+    bounds = list(struct.unpack_from("<%dH" % n, rec, _KEY_HEAD.size + 2))
+    if any(bytes(rec[off:body])):
+        raise ValueError("bounded keyframe record: padding bytes are not zero")
+    stream = memoryview(rec)[body:]
+    cnt, bits, size = stream_info(stream)
+    if cnt != h * w * n or bits != 8 * item or size != len(stream):
+        raise ValueError("bounded keyframe record: a stream of %d %d-bit samples in %d bytes for a %dx%dx%d frame of %d-byte samples"
+                         % (cnt, bits, len(stream), h, w, n, item))
+    return {"height": h, "width": w, "itemsize": item, "channels": channels, "yuv": yuv, "bounds": bounds, "stream": stream}
+
+
 def _split(raw, sizes):
     out, off = [], 0
     for s in sizes:
@@ -135,6 +183,22 @@ class SampleCoder:
         nat.check(nat.lib().rbf_rice_encode_intra(self.ctx.handle, fb.ptr, a.nbytes, len(arrs), W, H, C, a.dtype.itemsize, ob.ptr, ob.nbytes, sizes))
         return _split(ob.download(sum(sizes)).tobytes(), sizes)
 
+    def encode_near(self, frames_ptr, frame_stride, nframes, indices, width, height, channels, sample_bytes, bounds):
+        """Type-7 streams of the frames `indices` (ascending, each < nframes) of a resident dense block, which become their rebuilt frames
+        Y IN PLACE (rbf_rice_encode_intra_near): ONE launch sequence, one exact-size download.  bounds: `channels` per-channel bounds."""
+        idx = [int(i) for i in indices]
+        if not idx or any(not 0 <= i < nframes for i in idx) or any(b <= a for a, b in zip(idx, idx[1:])):
+            raise ValueError("frame indices %r: ascending indices inside the block of %d frames" % (idx, nframes))
+        d = [int(v) for v in bounds]
+        if len(d) != channels or any(v < 0 or v >> 32 for v in d):
+            raise ValueError("bounds %r: one non-negative bound for each of the %d channels" % (list(bounds), channels))
+        cap = len(idx) * max_stream_bytes(width * height * channels, 8 * sample_bytes)
+        ob = self._buf("streams", cap)
+        sizes = (ctypes.c_uint64 * len(idx))()
+        nat.check(nat.lib().rbf_rice_encode_intra_near(self.ctx.handle, frames_ptr, frame_stride, (ctypes.c_uint32 * len(idx))(*idx), len(idx), width,
+                                                       height, channels, sample_bytes, (ctypes.c_uint32 * channels)(*d), ob.ptr, ob.nbytes, sizes))
+        return _split(ob.download(sum(sizes)).tobytes(), sizes)
+
     def encode_inter(self, frames_ptr, frame_stride, nframes, width, height, channels, sample_bytes, masks_ptr, mask_stride, ones):
         """Type-4 streams of the nframes-1 pairs of resident dense frames under their packed masks (rbf_rice_encode_inter): ONE launch
         sequence, one exact-size download.  ones: the masks' set-bit counts."""
@@ -166,6 +230,24 @@ class SampleCoder:
         fb = self._buf("frame", nbytes)
         src = np.frombuffer(stream, dtype=np.uint8)
         nat.check(nat.lib().rbf_rice_decode_intra(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, fb.ptr))
+        if on_decoded is not None:
+            on_decoded(fb.ptr, nbytes, 1)
+        out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
+        return out.reshape((height, width) if channels == 0 else (height, width, C))
+
+    def decode_near_frame(self, stream, height, width, channels, itemsize, bounds, on_decoded=None):
+        """decode_frame for a type-7 stream: the rebuilt frame Y (rbf_rice_decode_intra_near); bounds: the record's per-channel bounds."""
+        C = max(1, channels)
+        nbytes = height * width * C * itemsize
+        fb = self._buf("frame", nbytes)
+        src = np.frombuffer(stream, dtype=np.uint8)
+        d = (ctypes.c_uint32 * C)(*_near_bounds(bounds, C))
+        try:
+            nat.check(nat.lib().rbf_rice_decode_intra_near(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, d, fb.ptr))
+        except nat.RbfError as e:
+            if e.code != nat.RBF_EINVAL:
+                raise
+            raise ValueError("corrupt bounded keyframe record: %s" % e) from None      # (the record's bytes are wrong, not the call)
         if on_decoded is not None:
             on_decoded(fb.ptr, nbytes, 1)
         out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)

@@ -23,7 +23,7 @@ _REFUSALS = {"gop_batching": lambda f, name: "%s needs gop_batching=True: the fr
              "all_channels": lambda f, name: "%s %s every sample of a pixel: it needs mask_channels='all'" % (name, f.verb)}
 
 Options = namedtuple("Options", "pan_range error_bounds quality_report scene_cuts max_error hold_mode frame_digests verify_digests near "
-                                "sample_codec mask_channels inter_frames keyframe_interval gop_batching block_frames gpu_lanes")
+                                "sample_codec mask_channels inter_frames keyframe_interval gop_batching block_frames gpu_lanes bounded_keyframes")
 
 
 def _is_int(v):
@@ -39,7 +39,7 @@ def _require(feature, name, have):
 
 def check_options(keyframe_interval=30, inter_frames=None, gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma",
                   sample_codec="zlib", max_error=0, frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False,
-                  error_bounds=None, quality_report=False, pan_range=0):
+                  error_bounds=None, quality_report=False, pan_range=0, bounded_keyframes=False):
     """The checked and normalised keywords of ImprovedVideoCompressor as an Options tuple, or the ValueError of the first refusal.
     `near` is the name the near-lossless stage goes by in messages ("error_bounds", "max_error > 0") or None.  The default block is
     two keyframe intervals (a multiple of the interval: every block of a stream has the same shape), at most 128 frames: small blocks
@@ -78,11 +78,22 @@ def check_options(keyframe_interval=30, inter_frames=None, gop_batching=True, bl
         raise ValueError("sample_codec must be 'zlib' or 'rice', got %r" % (sample_codec,))
     if sample_codec == "rice" and inter_frames is False:
         raise ValueError("sample_codec='rice' writes 'BFV2' records; inter_frames=False asks for 'BFVC', which holds zlib keyframes only")
+    if bounded_keyframes:
+        if sample_codec != "rice":
+            raise ValueError("bounded_keyframes=True writes type-7 records, whose payload is a sample stream: it needs sample_codec='rice'")
+        if not near:
+            raise ValueError("bounded_keyframes=True codes keyframes within the near-lossless bound: it needs max_error > 0 or error_bounds")
+        e = None if error_bounds is None else container.bounds_frame(error_bounds)
+        if e is not None and e.ndim >= 2:
+            raise ValueError("bounded_keyframes=True: a type-7 record carries one bound per channel, and a decoder would need the map: "
+                             "not with error_bounds of shape %r" % (e.shape,))
+        if e is not None and not e.any():
+            raise ValueError("bounded_keyframes=True needs a bound: error_bounds is all zero")
     I = max(1, int(keyframe_interval))
     block_frames = max(2, int(block_frames)) if block_frames else min(128, max(2, 2 * I if 2 * I <= 128 else I))
     return Options(pan_range, error_bounds, bool(quality_report), bool(scene_cuts), max_error, hold_mode, bool(frame_digests),
                    bool(verify_digests), near, sample_codec, mask_channels, inter_frames, I, bool(gop_batching), block_frames,
-                   max(1, int(gpu_lanes)))
+                   max(1, int(gpu_lanes)), bool(bounded_keyframes))
 
 
 def check_blocks(options, blocks, first_index, I):

@@ -10,7 +10,8 @@ mask of every pixel in which any sample changed instead, which covers every chan
 
 Container and record types: container.py.  sample_codec="rice" writes types 3 and 4 instead of 1 and 2: the same two roles with the GPU
 sample codec (sample_codec.py) in place of zlib-9.  frame_digests=True appends a type-5 record: one digest per frame (integrity.py), which
-decompress_video checks against what it rebuilt.
+decompress_video checks against what it rebuilt.  bounded_keyframes=True writes type 7 where a near-lossless call would write type 3: the
+keyframe within the bound, quantised in the block it is resident in (rbf_kernels_keyquant.h).
 """
 import contextlib
 import os
@@ -27,10 +28,10 @@ import numpy as np
 from . import container
 from . import params as P
 from ._native import frame_geometry
-from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_RICE, KEYS, PANS, is_keyframe, plan_range
+from .container import DIGESTS, INTER, INTER_RICE, KEY, KEY_NEAR, KEY_RICE, KEY_TYPES, PANS, is_keyframe, plan_range
 from .frame_codec import FixedVideoCompressor, VideoFrameCompressor, YUVFrame, build_record, frame_data, parse_record
 from .integrity import IntegrityError, build_trailer, digests_device, frame_digest_host
-from .sample_codec import key_format, key_record, parse_key_record, stream_info
+from .sample_codec import key_format, key_record, near_key_record, parse_key_record, parse_near_key_record, stream_info
 from .surface_options import check_blocks, check_options
 
 _POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)   # numpy 1.x has no bitwise_count
@@ -152,13 +153,14 @@ _CoderSpec = namedtuple("_CoderSpec", "width height nframes channels sample_byte
 class _BlockRecords:
     """What _encode_block returns for a block the GPU coded."""
 
-    def __init__(self, pairs=(), digests=None, cuts=(), pan_offsets=None, pans=(), quality=None):
+    def __init__(self, pairs=(), digests=None, cuts=(), pan_offsets=None, pans=(), quality=None, near_keys=None):
         self.pairs = list(pairs)                 # per pair: the future of its inter-frame record, or None (needs a keyframe, or is one)
         self.digests = digests                   # frame_digests=True: uint64 per frame of the block, or None
         self.cuts = tuple(cuts)                  # scene_cuts=True: the block indices the cut rule made run starts
         self.pan_offsets = pan_offsets           # pan_range > 0: the frames' cumulative offsets (ox, oy) in the block, or None
         self.pans = pans                         # ... and [(block index, dx, dy)] of the pairs that adopted a shift
         self.quality = quality                   # quality_report=True: GopCoder.error_stats() of the block, a row per frame
+        self.near_keys = near_keys or {}         # bounded_keyframes=True: block index of a run first -> its type-7 record
 
 
 def _union_seconds(intervals):
@@ -241,6 +243,19 @@ class _RangeRecords:
         else:
             self.pending[t] = (KEY, self.comp.compressor.compress_frame_jobs(frame, self.pool.submit))
 
+    def near_key(self, u, got, j):
+        """Frame u is a run first of a block: True when the block delivered its type-7 record (bounded_keyframes: the block holds the
+        quantised frame Y, and the inter-frames behind it hang off Y), which is filed -- the frame no longer goes through gpu_keys, and
+        its row of the quality report is the block's, like its digest.  Two blocks that hold the same keyframe deliver the same bytes."""
+        rec = got.near_keys.get(j)
+        if rec is None or not self.start <= u < self.stop:
+            return rec is not None
+        self.gpu_keys.discard(u)
+        self.records.setdefault(u, (KEY_NEAR, rec))
+        if got.quality is not None:
+            self.quality.setdefault(u, got.quality[j])
+        return True
+
     def digest_of(self, u, block_digests=None, j=0):
         """Frame u's digest: entry j of its block's (taken on the GPU from the resident frames), else the host twin's of the caller's array."""
         if not self.comp.frame_digests or u in self.digests or not self.start <= u < self.stop:
@@ -265,11 +280,13 @@ class _RangeRecords:
         cut = set(got.cuts)                      # a cut frame is a run start of its block like a rule keyframe
         self.scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
         self.pans += [(lo + j, dx, dy) for j, dx, dy in got.pans if start <= lo + j < stop]
+        self.near_key(lo, got, 0)
         self.digest_of(lo, got.digests, 0)
         for j in range(1, len(seg)):
             u = lo + j
             if is_keyframe(u, self.first_index, comp.keyframe_interval) or j in cut:
-                self.key(u)
+                if not self.near_key(u, got, j):
+                    self.key(u)
                 self.digest_of(u, got.digests, j)
                 continue
             if inter is None:
@@ -294,7 +311,7 @@ class _RangeRecords:
         comp, frames, first_index, start, stop = self.comp, self.frames, self.first_index, self.start, self.stop
         if self.gpu_keys:
             t_key = time.perf_counter()
-            for u, rec in comp._encode_keys_rice(frames, first_index, sorted(self.gpu_keys), busy).items():
+            for u, rec in comp._encode_keys_rice(frames, first_index, sorted(self.gpu_keys - set(self.records)), busy).items():
                 self.records[u] = (KEY_RICE, rec)
             if release:
                 comp._release_lanes()
@@ -315,8 +332,8 @@ class ImprovedVideoCompressor:
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
                  frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False, error_bounds=None, quality_report=False,
-                 pan_range=0):
-        """Reference signature (improved_video_compressor.py:318-327) plus fifteen keyword-only extras:
+                 pan_range=0, bounded_keyframes=False):
+        """Reference signature (improved_video_compressor.py:318-327) plus sixteen keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -397,13 +414,30 @@ class ImprovedVideoCompressor:
         max_error > 0 does); not with error_bounds that differ from pixel to pixel (the bound map would no longer sit on the pixels it
         was drawn for; per-channel bounds are fine).  A block whose frames are not larger than 2R in both directions is coded as
         without the keyword.  last_pans lists (global frame index, dx, dy) for every pair of the last encode_range that adopted a shift.
+        bounded_keyframes: False (default) -- keyframes are exact, nothing is launched and the container is today's, byte for byte.
+        True -- every keyframe that is a run first of a batched block (rule keyframes and scene cuts alike) is coded within the bound
+        instead of exactly: a closed-loop quantiser inside the keyframe predictor (GopCoder.quantise_run_starts:
+        rbf_rice_encode_intra_near, include/rbf.h has the rule) rewrites the frame in its block before the hold runs, so the
+        inter-frames that hang off it are held against the value a decoder will have, and the frame travels in a type-7 record
+        (container.KEY_NEAR: the per-channel bounds and a sample stream of the quantised residuals).  On noisy footage the exact
+        keyframes are the larger part of a near-lossless container; this takes 30-40 % off them.  The inter-frames are then held against
+        a keyframe that is up to d away from the original: the look-ahead hold absorbs that (the container shrinks), the first-value hold
+        does not when the noise is half the bound (the container can grow) -- use it with hold_mode="lookahead".  Needs sample_codec="rice" and a
+        near-lossless bound -- max_error > 0 or per-channel error_bounds that are not all zero; not error_bounds arrays of two or
+        more dimensions (a decoder would need the map) -- and with it everything max_error > 0 needs.  Combines with scene_cuts,
+        hold_mode, frame_digests, quality_report (a keyframe's row is then its block's, no longer zeros) and pan_range.  A keyframe
+        that never sits in a batched block -- an unbatchable shape, a keyframe outside any block, a frame no type-3 record could carry,
+        the exact fallback of a near-lossless run -- stays an exact record, which satisfies the bound.  A fresh default compressor
+        decodes the container.
         What the last call left behind: last_compressed_frames -- [(type, record bytes)] of compress_video; of encode_range last_digests,
         last_quality, last_scene_cuts and last_pans as above, and last_pan_offsets -- {index into its records: (ox, oy)}, what the
         type-6 record says; of decompress_video last_integrity -- {"frames", "checked", "device", "host"} -- and last_bad_frames -- the
         frames whose digest did not match (on_mismatch="collect"); of either last_timing -- seconds per stage (bench.py's e2e_surface
         leg; profile_stages=True synchronises between the stages of a block so that it can tell them apart)."""
         o = self._options = check_options(keyframe_interval, inter_frames, gop_batching, block_frames, gpu_lanes, mask_channels, sample_codec,
-                                          max_error, frame_digests, verify_digests, hold_mode, scene_cuts, error_bounds, quality_report, pan_range)
+                                          max_error, frame_digests, verify_digests, hold_mode, scene_cuts, error_bounds, quality_report, pan_range,
+                                          bounded_keyframes)
+        self.bounded_keyframes = o.bounded_keyframes
         self.pan_range, self.error_bounds, self.quality_report, self.scene_cuts = o.pan_range, o.error_bounds, o.quality_report, o.scene_cuts
         self.max_error, self.hold_mode, self._near = o.max_error, o.hold_mode, o.near
         self.frame_digests, self.verify_digests = o.frame_digests, o.verify_digests
@@ -609,7 +643,16 @@ class ImprovedVideoCompressor:
         tol = container.stat_tolerance(spec.max_error, None if spec.error_bounds is None else spec.error_bounds.min(), spec.hold_mode, sb)
         t1 = time.perf_counter()
         _, offsets, adopted, cuts, (t_up, t_pan) = self._prepare_block(coder, block, run_starts, tol)
+        t_q = time.perf_counter()
+        near_keys = {}
+        if self.bounded_keyframes:               # the run firsts become their quantised selves before the hold looks at them
+            firsts = [j for j in [0] + sorted(set(run_starts) | set(cuts)) if key_format(seg[j]) is not None]
+            bounds = coder.key_bounds()
+            near_keys = {j: near_key_record(seg[j], bounds, stream)
+                         for j, stream in coder.quantise_run_starts(lane.sample_coder(), firsts).items()}
         t2 = time.perf_counter()
+        if self.bounded_keyframes:
+            self._tm_add(key_quantise=t2 - t_q)
         coder.encode()
         if self.profile_stages:
             lane.ctx.sync()
@@ -628,14 +671,14 @@ class ImprovedVideoCompressor:
         t5 = time.perf_counter()
         self._tm_add(stack=t1 - t0, upload=t_up - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
         if self.scene_cuts:
-            self._tm_add(cut_stats=t2 - t_pan)   # (one launch sequence, a wait and 24 bytes per pair)
+            self._tm_add(cut_stats=t_q - t_pan)   # (one launch sequence, a wait and 24 bytes per pair)
         if self.pan_range:
             self._tm_add(pan_align=t_pan - t_up)
         if busy is not None:
             busy.append((t1, t5))
         fallback = container.fallback_pairs([bool(r.get("skipped")) for r in res], uncovered, offsets, self._near)
         return _BlockRecords(self._pair_jobs(res, values, fallback, pool, H * W, C, a.dtype.itemsize, rice),
-                             block_digests, cuts, offsets, adopted, block_quality)
+                             block_digests, cuts, offsets, adopted, block_quality, near_keys)
 
     def encode_range(self, frames, first_index, start, stop, inter_frames=True, release=True):
         """[(type, record)] for the frames with global indices [start, stop); frames[i] is global frame
@@ -725,15 +768,18 @@ class ImprovedVideoCompressor:
         outs = self._on_lanes(batches, run)
         return {t: rec for (_, ts_b), recs in zip(batches, outs) for t, rec in zip(ts_b, recs)}
 
-    def _decode_key_rice(self, rec, lane=None, busy=None, digest_out=None):
-        """A type-3 keyframe decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so.  digest_out: a list that
+    def _decode_key_rice(self, rec, lane=None, busy=None, digest_out=None, near=False):
+        """A type-3 keyframe (near: a type-7 one) decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so.  digest_out: a list that
         receives the frame's digest, taken on the device where the frame was decoded, before its download."""
-        d = parse_key_record(rec)
+        d = parse_near_key_record(rec) if near else parse_key_record(rec)
         if lane is None:
             lane = self._get_lanes(1)[0]
         t0 = time.perf_counter()
         hook = None if digest_out is None else (lambda ptr, nbytes, cnt: digest_out.extend(int(x) for x in lane.digests(ptr, nbytes, cnt, nbytes)))
-        frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], on_decoded=hook)
+        if near:
+            frame = lane.sample_coder().decode_near_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], d["bounds"], on_decoded=hook)
+        else:
+            frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], on_decoded=hook)
         if busy is not None:
             busy.append((t0, time.perf_counter()))
         return YUVFrame(frame) if d["yuv"] else frame
@@ -762,7 +808,7 @@ class ImprovedVideoCompressor:
         if self.frame_digests:                   # the trailer: one digest per frame record, behind them all
             records = records + [(DIGESTS, build_trailer(self.last_digests))]
         self.last_compressed_frames = records
-        keyframes = sum(1 for ty, _ in records if ty in KEYS)
+        keyframes = sum(1 for ty, _ in records if ty in KEY_TYPES)
         if output_path:
             blob = container.write(records)
             os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
@@ -782,6 +828,8 @@ class ImprovedVideoCompressor:
             results.update(max_error=self.max_error, hold_mode=self.hold_mode)
         if self.error_bounds is not None:
             results.update(error_bounds=True, hold_mode=self.hold_mode)
+        if self.bounded_keyframes:
+            results["bounded_keyframes"] = sum(1 for ty, _ in records if ty == KEY_NEAR)
         if self.scene_cuts:
             results["scene_cuts"] = list(self.last_scene_cuts)
         if self.pan_range:
@@ -850,14 +898,14 @@ class ImprovedVideoCompressor:
             base = keys[k].result()[0] if types[k] == KEY else None          # (waits for the host's inflate without holding a lane)
             with take() as lane:
                 if base is None:
-                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=log.sink(k))
+                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
                 if lo is None:
                     return None
                 return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi],
                                         digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, hi))
         try:
             bases = {k for k, _, _ in runs}
-            jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty == KEY_RICE and j not in bases]     # lone type-3 keyframes: no run
+            jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty in (KEY_RICE, KEY_NEAR) and j not in bases]     # lone type-3 keyframes: no run
             if self.gop_batching and jobs:
                 for (_, lo, _), out in zip(jobs, self._on_lanes(jobs, run_job)):
                     if lo is not None:
@@ -872,7 +920,7 @@ class ImprovedVideoCompressor:
                         if log.checking:
                             log.got[i] = (digest, "host")
                     else:
-                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=log.sink(i)))
+                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=log.sink(i), near=types[i] == KEY_NEAR))
                     i += 1
                     continue
                 if i in decoded:
@@ -890,7 +938,7 @@ class ImprovedVideoCompressor:
         self.last_integrity, self.last_bad_frames = log.summary(len(frames))
         if self.last_bad_frames and on_mismatch == "raise":
             i = self.last_bad_frames[0]
-            raise IntegrityError(i, log.expected[i], log.got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEYS))
+            raise IntegrityError(i, log.expected[i], log.got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEY_TYPES))
         if output_path:
             self.save_frames_as_video(frames, output_path)
         if self.verbose:
