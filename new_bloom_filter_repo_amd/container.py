@@ -181,8 +181,10 @@ def fallback_pairs(skipped, uncovered, offsets, near):
     say (a luma mask, chroma moved alone), so the frame falls back to an exact keyframe.  In a near-lossless block (near) and in a run
     that carries a non-zero pan offset (offsets: the frames' cumulative offsets, or None) the rest of the run goes with it: its records
     continue the HELD or STABILISED frames, not the exact keyframe a decoder will have.
-    Under today's refusals that propagation cannot be reached from the surface: near and pan_range both need mask_channels="all", whose
-    uncovered counts are all zero.  It stays because it is what makes relaxing that constraint safe."""
+    near and pan_range both need mask_channels="all", whose uncovered counts are all zero on frames of two or more channels, so colour
+    clips never reach that propagation.  Single-channel frames do: their one sample goes through the luma rule whatever mask_channels
+    says, and at 16 bits that rule does not mark a change of exactly 0x8000 (the int16 wrap).  A near-lossless or panned
+    run of 16-bit grey frames with such a pixel falls back from that frame on (tests/surface_cases.py has such clips)."""
     pairs = len(skipped)
     panned = [False] * pairs                     # pair f belongs to a run that carries a non-zero offset
     if offsets is not None:

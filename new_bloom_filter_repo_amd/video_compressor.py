@@ -271,8 +271,8 @@ class _RangeRecords:
         The block's digests describe its frames AFTER the hold.  The hold never writes a run's first frame (rbf_kernels_hold.h: "frame
         first[y] is never written"), so the block's first frame and the keyframes inside it -- the run starts handed to the coder -- still
         are the caller's originals, which is what their keyframe records code: their digests are taken from the block too.  Not so a
-        frame that falls back to a keyframe with max_error > 0: its record codes the original, the block holds the held frame -- the
-        host twin digests the original."""
+        frame that falls back to a keyframe with max_error > 0, or in a run the alignment rolled: its record codes the original, the
+        block holds the held or rolled frame -- the host twin digests the original."""
         comp, start, stop = self.comp, self.start, self.stop
         lo, end, _ = block
         seg = self.frames[lo - self.first_index:end - self.first_index]      # predecessor + the frames lo+1..end-1
@@ -304,7 +304,8 @@ class _RangeRecords:
                     self.quality[u] = got.quality[j]
                 continue
             self.key(u)
-            self.digest_of(u, None if comp._near else got.digests, j)
+            rolled = got.pan_offsets is not None and got.pan_offsets[j] != (0, 0)     # (the block holds the frame rolled: the record codes the caller's)
+            self.digest_of(u, None if comp._near or rolled else got.digests, j)
 
     def finish(self, release, tm, busy):
         """Code the type-3 keyframes, wait for the host threads, set the compressor's last_* attributes; the range's [(type, record)]."""

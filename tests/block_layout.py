@@ -408,3 +408,46 @@ def far_roll_decoys_matter(x, decoys, offsets, want):
     import pan_ref
     return all(not np.array_equal(want[f], x[f]) for f in range(3)) and \
         all(not np.array_equal(pan_ref.roll(decoys[f - 1], *offsets[f]), want[f]) for f in (1, 2))
+
+
+# ------------------------------------------------------------------ the keyframe quantiser (rbf_rice_encode_intra_near): far frames, shared scratch
+FAR_KEYQUANT_CASES = [(np.uint8, 3, (1, 2, 2)), (np.uint16, 4, (2, 0, 3, 300))]      # (an exact channel among the bounded ones)
+FAR_KEYQUANT_IDS = ["u8c3", "u16c4"]
+FAR_KEYQUANT_LISTED = [1, 2]                                     # frame 0, at the block's base, is not listed: it has to stay as it is
+
+
+def far_keyquant_case(dtype, C, bounds):
+    """(x, decoys, want, streams): three 799x11 frames of which FAR_KEYQUANT_LISTED are quantised, the decoys of frames 1 and 2, the block
+    afterwards (frame 0 as it was, the listed frames their near_key_ref Y) and the listed frames' streams."""
+    import near_key_ref as nk
+    x, decoys = far_clip(8610 + C, dtype, C), list(far_clip(8710 + C, dtype, C)[1:])
+    want, streams = np.array(x), []
+    for f in FAR_KEYQUANT_LISTED:
+        want[f], s = nk.stream(x[f], list(bounds))
+        streams.append(s)
+    return x, decoys, want, streams
+
+
+def far_keyquant_decoys_matter(x, decoys, want, streams, bounds):
+    """A kernel that reads a decoy writes another stream (and another frame); one that writes Y over a decoy changes it, since the
+    quantiser changes the decoy as it changes the frame."""
+    import near_key_ref as nk
+    for k, f in enumerate(FAR_KEYQUANT_LISTED):
+        Yd, sd = nk.stream(decoys[f - 1], list(bounds))
+        if sd == streams[k] or np.array_equal(Yd, want[f]) or np.array_equal(Yd, decoys[f - 1]) or np.array_equal(want[f], x[f]):
+            return False
+    return bool(np.array_equal(want[0], x[0]))
+
+
+# (frames of the block, H, W, C or None for (H, W) frames, dtype, listed frames, bounds): the near-encode calls of the shared-scratch sequence
+KEYQUANT_STEPS = [(5, 37, 91, 3, np.uint8, [0, 2, 4], (1, 2, 2)),
+                  (2, 9, 21, None, np.uint16, [1], (3,)),
+                  (3, 64, 130, 4, np.uint16, [1], (2, 0, 3, 300))]
+KEYQUANT_ORDER = [0, 3, 1, 4, 2, 5, 0, 1, 3, 2, 4, 0]            # steps 3, 4, 5: rbf_rice_encode_inter, rbf_rice_decode_intra_near, rbf_rice_decode_intra
+
+
+def keyquant_step_sizes(step):
+    """(listed frames, samples of a frame, samples the call puts into the shared u buffer)."""
+    F, H, W, C, dtype, listed, bounds = step
+    n = H * W * (C or 1)
+    return len(listed), n, len(listed) * n

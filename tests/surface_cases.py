@@ -1,0 +1,244 @@
+"""The cases of the surface sweep, as data: which combinations of ImprovedVideoCompressor's keywords test_gpu_surface_twin.py runs against
+surface_twin.py, and why the others are not run.  Shared by test_surface_cases_cpu.py, which proves on the CPU that the legality
+predicate below is the constructor's, that CASES covers every legal pair of option values, and that every case's clip exercises what
+the case turns on.  A test helper: not collected.
+
+Read it top to bottom: AXES (the values), legal() (what may be combined, with the reason for every refusal), CASES (a pairwise covering
+array over the legal assignments, built by a small deterministic greedy generator), clip() (the input of a case)."""
+import itertools
+
+import numpy as np
+
+W, H, T, I = 96, 64, 19, 4                       # frames of W x H; T frames, a keyframe every I
+CUT = 10                                         # the spliced clips start their second scene here: inside the run 8 .. 11, no rule keyframe
+SHARDS = [(0, 8), (8, T)]                        # the shards of the "shards" cases: cut at a keyframe
+R = 4
+
+# near-lossless modes: constructor keywords, and the sensor noise of the clip they run on
+NEAR = {"off": dict(),
+        "first_d2": dict(max_error=2),
+        "look_d1": dict(max_error=1, hold_mode="lookahead"),
+        "first_122": dict(error_bounds=(1, 2, 2)),
+        "look_133": dict(error_bounds=(1, 3, 3), hold_mode="lookahead"),
+        "map": dict(error_bounds="MAP")}         # a per-pixel map: 2 everywhere, a rectangle of zeros (bound_map())
+NOISE = {"off": 1, "first_d2": 1, "look_d1": 1, "first_122": 1, "look_133": 2, "map": 1}
+# ... and its lighting step: frames 6 and 7 are brighter by this many levels in every sample.  A step within the statistic's tolerance is
+# no movement, one past it moves every pixel, so these pairs are where the cut rule shows which tolerance it was handed: the look-ahead
+# hold's doubled one (2 for look_d1: a step of 2 is still; not doubled, frame 6 is a cut) and the smallest entry of a bound frame (2 for
+# look_133: a step of 4 is a cut; from the largest entry, 6, it is still)
+STEP = {"off": 0, "first_d2": 0, "look_d1": 2, "first_122": 0, "look_133": 4, "map": 0}
+STEP_FRAMES = (6, 8)
+
+AXES = [("dtype", ["u8", "u16"]),
+        ("layout", ["grey", "yuv", "bgr"]),      # grey: (H, W) frames; yuv: (H, W, 3) handed in as YUV; bgr: (H, W, 3) handed in as BGR
+        ("mask_channels", ["luma", "all"]),
+        ("sample_codec", ["zlib", "rice"]),
+        ("near", list(NEAR)),
+        ("scene_cuts", [False, True]),
+        ("pan_range", [0, R]),
+        ("bounded_keyframes", [False, True]),
+        ("frame_digests", [False, True]),
+        ("quality_report", [False, True]),
+        ("gpu_lanes", [1, 2, 3]),
+        ("block_frames", [I, 2 * I, 3 * I, 6]),  # 6: no multiple of I -- blocks that start inside a run
+        ("route", ["whole", "shards"])]          # compress_video, or encode_range over SHARDS, each from its halo frame on
+NAMES = [name for name, _ in AXES]
+# Constructor keywords that change bytes and are no axis: keyframe_interval (I, fixed: the plan's arithmetic is in test_surface_plan_cpu.py),
+# inter_frames=False and gop_batching=False (no resident block: every feature of this sweep refuses them; test_gpu_surface.py holds their
+# bytes against the batched route).
+
+
+def bound_map():
+    e = np.full((H, W), 2, dtype=np.int64)
+    e[16:40, 24:72] = 0
+    return e
+
+
+def legal(c):
+    """None when the assignment c (a dict over NAMES) can be run, else the reason it cannot.  Written out, not obtained from the
+    constructor: test_surface_cases_cpu.py proves the two agree on the full product of AXES."""
+    near, pan = c["near"] != "off", c["pan_range"] > 0
+    if near and c["mask_channels"] != "all":
+        return "the hold holds every sample of a pixel: near-lossless needs mask_channels='all'"
+    if pan and c["mask_channels"] != "all":
+        return "the roll moves every sample of a pixel: pan_range needs mask_channels='all'"
+    if (near or pan) and c["block_frames"] % I:
+        return "held state and cumulative offsets live in one block's coder: every block must start at a keyframe"
+    if pan and c["near"] == "map":
+        return "pan_range moves the pixels from under a per-pixel bound map"
+    if c["near"] in ("first_122", "look_133") and c["layout"] == "grey":
+        return "three per-channel bounds do not fit frames of one channel"
+    if c["bounded_keyframes"]:
+        if c["sample_codec"] != "rice":
+            return "a type-7 record's payload is a sample stream: bounded_keyframes needs sample_codec='rice'"
+        if not near:
+            return "bounded_keyframes codes keyframes within the near-lossless bound: it needs one"
+        if c["near"] == "map":
+            return "a type-7 record carries one bound per channel, not a map"
+    return None
+
+
+def keywords(c):
+    """The constructor keywords of a case."""
+    kw = dict(keyframe_interval=I, block_frames=c["block_frames"], gpu_lanes=c["gpu_lanes"], mask_channels=c["mask_channels"],
+              sample_codec=c["sample_codec"], scene_cuts=c["scene_cuts"], pan_range=c["pan_range"], bounded_keyframes=c["bounded_keyframes"],
+              frame_digests=c["frame_digests"], quality_report=c["quality_report"])
+    kw.update(NEAR[c["near"]])
+    if kw.get("error_bounds") == "MAP":
+        kw["error_bounds"] = bound_map()
+    if c["layout"] != "yuv":
+        kw["inter_frames"] = True                # (inter-frames are the default for YUV input only)
+    return kw
+
+
+def color_space(c):
+    return "YUV" if c["layout"] == "yuv" else "BGR"
+
+
+def shards(c):
+    return SHARDS if c["route"] == "shards" else None
+
+
+def frame_shape(c):
+    return (H, W) if c["layout"] == "grey" else (H, W, 3)
+
+
+def frame_dtype(c):
+    return np.uint8 if c["dtype"] == "u8" else np.uint16
+
+
+# ---- the covering array ----------------------------------------------------------------------------------------------------------------
+def product():
+    """Every assignment of AXES, as dicts (itertools.product order)."""
+    for values in itertools.product(*[v for _, v in AXES]):
+        yield dict(zip(NAMES, values))
+
+
+def _index_table():
+    """(idx, legal mask): the full product as an (N, axes) array of value indices, and which rows are legal."""
+    sizes = [len(v) for _, v in AXES]
+    idx = np.indices(sizes).reshape(len(sizes), -1).T
+    ok = np.array([legal({n: AXES[a][1][row[a]] for a, n in enumerate(NAMES)}) is None for row in idx])
+    return idx, ok
+
+
+def legal_pairs(idx):
+    """{(axis a, axis b): set of (value index, value index)} over the rows of idx, a < b."""
+    out = {}
+    for a, b in itertools.combinations(range(len(AXES)), 2):
+        out[(a, b)] = {(int(x), int(y)) for x, y in np.unique(idx[:, [a, b]], axis=0)}
+    return out
+
+
+def covering_array():
+    """A pairwise covering array over the legal assignments, greedily: take the legal assignment that covers the most pairs not covered
+    yet (the first of them in product order), until none is left.  Deterministic, numpy only."""
+    idx, ok = _index_table()
+    rows = idx[ok]
+    sizes = [len(v) for _, v in AXES]
+    axis_pairs = list(itertools.combinations(range(len(AXES)), 2))
+    codes = {(a, b): rows[:, a] * sizes[b] + rows[:, b] for a, b in axis_pairs}
+    open_ = {}
+    for (a, b), code in codes.items():
+        t = np.zeros(sizes[a] * sizes[b], dtype=bool)
+        t[np.unique(code)] = True
+        open_[(a, b)] = t
+    cases = []
+    while True:
+        score = np.zeros(len(rows), dtype=np.int64)
+        for ab, code in codes.items():
+            score += open_[ab][code]
+        best = int(score.argmax())
+        if score[best] == 0:
+            break
+        for ab, code in codes.items():
+            open_[ab][code[best]] = False
+        cases.append({n: AXES[a][1][rows[best][a]] for a, n in enumerate(NAMES)})
+    return cases
+
+
+def case_id(k, c):
+    on = [n for n in ("scene_cuts", "bounded_keyframes", "frame_digests", "quality_report") if c[n]]
+    short = {"scene_cuts": "cuts", "bounded_keyframes": "key7", "frame_digests": "fd", "quality_report": "q"}
+    return "-".join(["%02d" % k, c["dtype"], c["layout"], c["mask_channels"], c["sample_codec"], c["near"]] + (["pan"] if c["pan_range"] else [])
+                    + [short[n] for n in on] + ["l%d" % c["gpu_lanes"], "b%d" % c["block_frames"], c["route"]])
+
+
+# Beyond the pairs: combinations of three values that reach code no pair does.
+#   16-bit grey frames under pan_range: their one sample goes through the luma rule, blind to a change of 0x8000, so a panned run
+#   falls back to exact keyframes from such a frame on -- whose digests must be those of the caller's frames, not of the rolled block's
+EXTRA = [dict(dtype="u16", layout="grey", mask_channels="all", sample_codec="rice", near="off", scene_cuts=False, pan_range=R,
+              bounded_keyframes=False, frame_digests=True, quality_report=True, gpu_lanes=2, block_frames=2 * I, route="whole")]
+CASES = covering_array() + EXTRA
+IDS = [case_id(k, c) for k, c in enumerate(CASES)]
+
+
+def invariance_cases():
+    """One case per near-lossless mode and sample type (where CASES has one) whose blocks start at keyframes: the subset the knob
+    invariants run on, in the twin and on the GPU."""
+    picked = {}
+    for k, c in enumerate(CASES):
+        if c["block_frames"] % I == 0:
+            picked.setdefault((c["near"], c["dtype"]), k)
+    return sorted(picked.values())
+
+
+# ---- the clips -------------------------------------------------------------------------------------------------------------------------
+# kind of clip by what the case turns on; the seeds were chosen so that the conditions of test_surface_cases_cpu.py hold (they are
+# conditions on the twin's output, proven there, not measurements of the product)
+SEEDS = {"static": (706, 707), "pan": (11, 12), "gop": (701, 702)}
+_clips = {}
+
+
+def clip_name(c):
+    """static: two camera scenes spliced at CUT, sensor noise.  pan: the same under a camera that pans by (2, 1) a frame.  gop: two
+    make_gop scenes (every changed pixel changes its luma) with frame 5 = frame 4 but for one chroma sample -- the clip of the colour
+    cases with a luma mask, where the camera clips would lose every inter-frame."""
+    if c["pan_range"]:
+        kind = "pan"
+    elif c["mask_channels"] == "luma" and c["layout"] != "grey":
+        kind = "gop"
+    else:
+        kind = "static"
+    return (kind, NOISE[c["near"]], c["dtype"], c["layout"], 0 if kind == "gop" else STEP[c["near"]])
+
+
+def clip(c):
+    """The T frames of a case: a list of arrays (never written to: copy before handing them to anything that might)."""
+    from new_bloom_filter_repo_amd.synthetic import make_camera_gop, make_gop, make_panning_gop
+    name = clip_name(c)
+    if name not in _clips:
+        kind, noise, dt, layout, step = name
+        dtype = np.uint8 if dt == "u8" else np.uint16
+        space = "BGR" if layout == "bgr" else "YUV"
+        a, b = SEEDS[kind]
+        if kind == "static":
+            frames = (make_camera_gop(a, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
+                      + make_camera_gop(b, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
+        elif kind == "pan":
+            frames = (make_panning_gop(a, W, H, T, (2, 1), dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
+                      + make_panning_gop(b, W, H, T, (2, 1), dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
+        else:
+            frames = [f.copy() for f in make_gop(a, W, H, T, p=0.08, dtype=dtype)[:CUT] + make_gop(b, W, H, T, p=0.08, dtype=dtype)[CUT:]]
+            frames[5] = frames[4].copy()
+            frames[5][3, 7, 1] ^= 1
+        for t in range(*STEP_FRAMES):
+            frames[t] = np.clip(frames[t].astype(np.int64) + step, 0, np.iinfo(dtype).max).astype(dtype)
+        if layout == "grey":
+            frames = [np.ascontiguousarray(f[..., 0]) for f in frames]
+        for f in frames:
+            f.setflags(write=False)
+        _clips[name] = frames
+    return _clips[name]
+
+
+# ---- the twin's output per case, computed once --------------------------------------------------------------------------------------------
+_twins = {}
+
+
+def twin_of(k, mutant=None):
+    import surface_twin
+    if (k, mutant) not in _twins:
+        c = CASES[k]
+        _twins[(k, mutant)] = surface_twin.twin(clip(c), keywords(c), shards(c), mutant)
+    return _twins[(k, mutant)]

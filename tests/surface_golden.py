@@ -28,7 +28,8 @@ GRID = [("gop_batching", [True, False]),
         ("hold_mode", ["first", "lookahead", "x"]),
         ("scene_cuts", [False, True]),
         ("error_bounds", [None, (1, 2, 2), _MAP, "2"]),
-        ("pan_range", [0, 4, 33, True])]
+        ("pan_range", [0, 4, 33, True]),
+        ("bounded_keyframes", [False, True])]
 SYMBOLS = string.ascii_letters + string.digits
 
 
@@ -130,6 +131,7 @@ CONFIGS = [
     ("defaults_one_lane", "gop8", dict(gpu_lanes=1), {}),
     ("defaults_blocks_of_6", "gop8", dict(block_frames=6), {}),
     ("shards", "gop8", {}, dict(shards=[(0, 6), (6, T)])),
+    ("bounded_keyframes", "noise1", dict(mask_channels="all", sample_codec="rice", max_error=2, bounded_keyframes=True), {}),
 ]
 SAME_BYTES = [("bounds_uniform", "max_error_2"), ("defaults_one_lane", "defaults"), ("defaults_blocks_of_6", "defaults")]
 QUALITY_INTS = ("max_abs_error", "changed_samples", "over_bound")
@@ -138,7 +140,7 @@ QUALITY_INTS = ("max_abs_error", "changed_samples", "over_bound")
 def canonical_hash(records):
     """sha256 over a container's records in a form that does not depend on the zlib build: per record the type byte, then for type 1 the
     decoded frame (shape, dtype, whether it carries planes, bytes), for type 2 the record's fields with the value field inflated, for types
-    3 to 6 the raw body."""
+    3 to 7 the raw body."""
     from new_bloom_filter_repo_amd.frame_codec import FixedVideoCompressor, YUVFrame, frame_data, parse_record
     h = hashlib.sha256()
     keys = FixedVideoCompressor(verbose=False)

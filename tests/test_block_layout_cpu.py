@@ -136,3 +136,28 @@ def test_lane_clips_are_not_vacuous(dtype, C):
         assert bl.lane_non_vacuous(x, hold_ref(x, bl.LANE_STARTS, e), bl.HOLD_LANE_PIXELS), ("hold", e)
         assert bl.lane_non_vacuous(x, lookahead_ref(x, bl.LANE_STARTS, e)[0], bl.LOOKAHEAD_LANE_PIXELS), ("lookahead", e)
     assert bl.cut_non_vacuous(x, 1)
+
+
+# ------------------------------------------------------------------ the keyframe quantiser's far frames and its shared-scratch sequence
+@pytest.mark.parametrize("dtype,C,bounds", bl.FAR_KEYQUANT_CASES, ids=bl.FAR_KEYQUANT_IDS)
+def test_far_keyquant_frames_pass_2_31_and_2_32_and_their_decoys_matter(dtype, C, bounds):
+    x, decoys, want, streams = bl.far_keyquant_case(dtype, C, bounds)
+    assert x[0].nbytes in FRAME_BYTES, "test_far_frames checks this layout"
+    lay = bl.far_frames(x[0].nbytes)
+    offsets = [lay.items[f] - lay.base for f in bl.FAR_KEYQUANT_LISTED]
+    assert offsets[0] >= 1 << 31 and offsets[1] >= 1 << 32, "frame_index[f] * frame_stride of the listed frames"
+    assert all(lay.aliases[f] for f in bl.FAR_KEYQUANT_LISTED) and 0 not in bl.FAR_KEYQUANT_LISTED
+    assert bl.far_keyquant_decoys_matter(x, decoys, want, streams, bounds)
+    assert 0 in bounds or C == 3, "one of the cases has an exact channel"
+
+
+def test_the_keyquant_sequence_shrinks_and_grows_in_count_and_in_frame_size():
+    sizes = [bl.keyquant_step_sizes(bl.KEYQUANT_STEPS[i]) for i in bl.KEYQUANT_ORDER if i < len(bl.KEYQUANT_STEPS)]
+    for what in range(3):                        # the count of listed frames, a frame's samples, the samples in the shared u buffer
+        seq = [s[what] for s in sizes]
+        ups, downs = [b > a for a, b in zip(seq, seq[1:])], [b < a for a, b in zip(seq, seq[1:])]
+        assert any(ups) and any(downs) and downs.index(True) < len(ups) - 1 - ups[::-1].index(True), (what, seq)
+    order = bl.KEYQUANT_ORDER
+    assert set(order) == set(range(6)) and all(a != b for a, b in zip(order, order[1:])), "every step, none twice in a row"
+    # every near-encode call is followed, somewhere, directly by each of the three stages that share its u buffer
+    assert {b for a, b in zip(order, order[1:]) if a < 3 and b >= 3} == {3, 4, 5}

@@ -241,3 +241,23 @@ def test_make_panning_gop():
     canvas = make_camera_gop(9, 40 + 12, 32 + 10, 3)
     assert all(np.array_equal(s, c[5:37, 6:46]) for s, c in zip(still, canvas))
     # the existing generators return the bytes they did (test_near_lossless_cpu.py pins make_camera_gop's digests)
+
+
+def test_a_fallen_back_frame_of_a_rolled_run_is_digested_from_the_callers_array():
+    """Its record codes the caller's frame; the block holds that frame rolled by the run's offset, so the block's digest is not the
+    frame's.  (Reached by 16-bit single-channel clips, whose mask is blind to a change of 0x8000: tests/surface_cases.py, EXTRA.)"""
+    from concurrent.futures import ThreadPoolExecutor
+    from new_bloom_filter_repo_amd.integrity import frame_digest_host
+    from new_bloom_filter_repo_amd.video_compressor import ImprovedVideoCompressor, _BlockRecords, _RangeRecords
+    frames = [np.full((8, 12), 1000 * t + 7, dtype=np.uint16) for t in range(4)]
+    comp = ImprovedVideoCompressor(keyframe_interval=4, block_frames=4, inter_frames=True, mask_channels="all", pan_range=2, frame_digests=True)
+    with ThreadPoolExecutor(2) as pool:
+        book = _RangeRecords(comp, frames, 0, 0, 4, pool)
+        coded = pool.submit(lambda: b"record")
+        block_digests = [11, 22, 33, 44]         # (of the rolled block: right for the frames the records code, wrong for a frame coded from the caller's array)
+        book.take_block((0, 4, []), _BlockRecords([coded, None, None], digests=block_digests, pan_offsets=[(0, 0), (2, 1), (4, 2), (0, 0)]))
+        got = [d if isinstance(d, int) else d.result() for d in (book.digests[u] for u in range(4))]
+    assert got[:2] == [11, 22], "the keyframe and the coded inter-frame: the block's digests"
+    assert got[2] == frame_digest_host(frames[2]) != 33, "fell back under a non-zero offset: the caller's frame"
+    assert got[3] == 44, "fell back at offset (0, 0): the block holds the caller's frame"
+    assert book.pan_table == {1: (2, 1)}

@@ -10,11 +10,16 @@ def test_every_combination_of_the_grid_has_the_recorded_outcome():
     want = sg.load(sg.REFUSALS)
     assert want["grid"] == sg.grid_description() and want["dropped_values"] == []
     outcomes, index = sg.refusal_table(ImprovedVideoCompressor)
-    assert len(index) == len(want["index"]) == 41472
+    assert len(index) == len(want["index"]) == 82944
     if (outcomes, index) != (want["outcomes"], want["index"]):          # name the first combination that differs
         names = [name for name, _ in sg.GRID]
         for i, values in enumerate(itertools.product(*[v for _, v in sg.GRID])):
             got, exp = outcomes[sg.SYMBOLS.index(index[i])], want["outcomes"][sg.SYMBOLS.index(want["index"][i])]
             assert got == exp, (dict(zip(names, values)), got, exp)
-    assert outcomes == want["outcomes"] and index == want["index"] and len(outcomes) == 24
-    assert outcomes[0] == "ok" and index.count(sg.SYMBOLS[0]) == 136
+    assert outcomes == want["outcomes"] and index == want["index"] and len(outcomes) == 27
+    assert outcomes[0] == "ok" and index.count(sg.SYMBOLS[0]) == 168
+    # bounded_keyframes is the grid's last keyword (the fastest): without it the table is the one recorded before the keyword existed
+    assert sg.GRID[-1] == ("bounded_keyframes", [False, True])
+    off = index[0::2]
+    assert len(off) == 41472 and len(set(off)) == 24 and off.count(sg.SYMBOLS[0]) == 136
+    assert all("bounded_keyframes" not in outcomes[sg.SYMBOLS.index(ch)] for ch in set(off))

@@ -37,6 +37,31 @@ def containers():
     return doc
 
 
+def extends(what, old, new):
+    """Writing over a committed fixture may only ADD to it: a grid that grew by keywords keeps the recorded outcome of every old
+    combination (the new keywords at their first value, the default), and every recorded container entry stays as it is.  Returns what
+    was compared, for the log; AssertionError otherwise."""
+    if what == "containers":
+        for name, entry in old["entries"].items():
+            assert new["entries"].get(name) == entry, "container entry %r changed" % name
+        return "%d recorded entries unchanged, %d new" % (len(old["entries"]), len(new["entries"]) - len(old["entries"]))
+    names = [name for name, _ in sg.GRID]        # (product order; the files are written with sorted keys)
+    assert set(names) == set(new["grid"]) >= set(old["grid"]) and all(new["grid"][n] == v for n, v in old["grid"].items()), "the grid's old axes changed"
+    sizes = [len(new["grid"][n]) for n in names]
+    added = [n not in old["grid"] for n in names]
+    restricted, stride = [], 1
+    strides = []
+    for size in reversed(sizes):
+        strides.insert(0, stride)
+        stride *= size
+    import itertools
+    for idx in itertools.product(*[range(1 if a else size) for a, size in zip(added, sizes)]):
+        restricted.append(new["outcomes"][sg.SYMBOLS.index(new["index"][sum(i * st for i, st in zip(idx, strides))])])
+    recorded = [old["outcomes"][sg.SYMBOLS.index(ch)] for ch in old["index"]]
+    assert restricted == recorded, "an old combination's outcome changed"
+    return "%d recorded outcomes unchanged under %s at their defaults" % (len(recorded), [n for n, a in zip(names, added) if a])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true", help="compare with the committed files instead of writing them")
@@ -53,6 +78,8 @@ def main():
             print("%s: %s" % (os.path.basename(path), "identical" if same else "DIFFERENT"))
             bad += not same
             continue
+        if os.path.exists(path):
+            print("%s: %s" % (os.path.basename(path), extends(what, sg.load(path), doc)))
         if args.out:
             os.makedirs(args.out, exist_ok=True)
             path = os.path.join(args.out, os.path.basename(path))
