@@ -291,16 +291,45 @@ int rbf_noise_moments_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame
                             uint64_t row_pitch_bytes, uint32_t pixel_stride_bytes,
                             uint32_t sample_bytes, int64_t *moments_dev, float *noise_dev);
 
+/* ---- rows of the Bloom entries: what is read, what is written, what is left alone ------------------------------------------------ */
+/* For rbf_bloom_encode_batch, rbf_bloom_decode_batch, rbf_pack_records and rbf_encode_runs_begin(_ex) / rbf_encode_gop_begin +
+ * rbf_encode_gop_finish (tests/test_gpu_bloom_row_sweep.py holds every sentence, byte for byte, under poisoned blocks):
+ *  - Row f of masks, filters or witnesses lies at base + f * stride_bytes, a 64-bit product: rows may be gigabytes apart.  Every stride is
+ *    a multiple of 8 and at least the minimum its entry states.  Every base -- masks_dev, filters_dev, witnesses_dev, stats_dev,
+ *    ones_dev, record_dev -- is a multiple of 8: the kernels address them as 64-bit words and add to stats_dev atomically.  Any other base
+ *    is RBF_EINVAL ("masks_dev must be 8-byte aligned", ...) before anything is enqueued, and nothing is written.  Nothing needs more than
+ *    8: rows that are not 16-byte aligned, or a stride that is no multiple of 16, take the kernels' 4- and 8-byte paths.
+ *  - Nothing is written outside [base, base + nframes * stride_bytes) of an output role, and input rows are never written.
+ *  - Mask rows as INPUT (encode, pack): the first ceil(n/64)*8 bytes of a row are the mask, the pad bits of its last word must be 0 (the
+ *    mask stage writes them so; the record of an m == 0 frame carries the word as it is).  Nothing behind them is read.
+ *  - Filter rows as OUTPUT: a coded row (m != 0) is written over its WHOLE STRIDE -- the filter's ceil(m/64)*8 bytes, bits past m zero,
+ *    followed by zeros up to filter_stride_bytes.  So filters_dev must be a block of nframes * filter_stride_bytes bytes: one sized for
+ *    the filters alone is overrun, and rows a stride of gigabytes apart cost gigabytes of stores.  The row of an m == 0 frame or of a
+ *    skipped pair has NO DEFINED CONTENT (the LDS insert kernels leave it alone, the generic path clears it).
+ *  - Witness rows as OUTPUT: the first stats[f][RBF_STAT_WITNESS_BITS] bits, zero-padded to a whole 64-bit word, are defined; what lies
+ *    behind that word in the row is unspecified (left alone or zeroed; nothing is written from byte ceil(n/64)*8 + 8 of a row on).  An
+ *    m == 0 frame or a skipped pair has zero bits: nothing of its row is defined.
+ *  - stats_dev as OUTPUT: all RBF_STATS_PER_FRAME words of every row; the reserved ones, and every word of an m == 0 frame or a skipped
+ *    pair, are 0.
+ *  - Mask rows as OUTPUT (decode; the mask stage of the runs entries): the first ceil(n/64)*8 bytes, pad bits 0; the rest of the row is
+ *    left alone.  A frame with m == 0 decodes to an all-zero mask (its filter and witness rows are not read); a skipped pair's row is zero.
+ *  - Filter and witness rows as INPUT (decode, pack): of a filter row the ceil(m/64)*8 bytes of the filter count -- what else the row
+ *    holds up to its stride may be read and is ignored; of a witness row only the words that hold the frame's witness_bits bits are
+ *    read, so decode takes any witness stride >= the largest ceil(witness_bits/64)*8 of the batch, below ceil(n/64)*8.
+ *  - record_dev: the header and the record's used bytes (word [2]) are written, nothing behind them. */
+
 /* ---- A4 + A5: insert + query/witness  (BloomFilterCompressor.compress loops, :232-253) --- */
 /* For each frame f: zero filter f, insert every '1' position of mask f
  * (RationalBloomFilter.add_index, :99-114), then test every position 0..n-1 in order
  * (check_index, :116-138) and append mask bit i to the witness when it passes.
  *   masks_dev     nframes packed masks, stride mask_stride_bytes
  *   params        nframes host structs
- *   filters_dev   out: nframes packed filters, stride filter_stride_bytes >= ceil(m/64)*8
+ *   filters_dev   out: nframes packed filters, stride filter_stride_bytes >= ceil(m/64)*8 for every m of the batch; a coded row is written
+ *                 over its whole stride, so the block is nframes * filter_stride_bytes bytes (rows of the Bloom entries, above)
  *   witnesses_dev out: nframes packed witnesses, stride witness_stride_bytes >= ceil(n/64)*8; the first stats[f][RBF_STAT_WITNESS_BITS]
  *                 bits of row f are the witness, zero-padded to whole 64-bit words -- what lies behind them in the row is unspecified
- *   stats_dev     out: nframes x RBF_STATS_PER_FRAME uint64 */
+ *   stats_dev     out: nframes x RBF_STATS_PER_FRAME uint64
+ * More than 128 frames are coded in chunks of 128 rows, each at its place in the caller's strides. */
 int rbf_bloom_encode_batch(rbf_ctx *ctx, const void *masks_dev, uint64_t mask_stride_bytes,
                            uint64_t n, uint32_t nframes, const rbf_filter_params *params,
                            const rbf_seeds *seeds,
@@ -413,7 +442,9 @@ int rbf_pack_records(rbf_ctx *ctx, uint32_t nframes, uint64_t n, const rbf_filte
                      const uint64_t *stats_dev, void *record_dev, uint64_t capacity_bytes);
 
 /* ---- A6: decode  (BloomFilterCompressor.decompress loop, :286-307) ------------------------ */
-/* out mask bit i = witness[w++] if position i passes the filter, else 0. */
+/* out mask bit i = witness[w++] if position i passes the filter, else 0.  filter_stride_bytes >= ceil(m/64)*8 for every m of the batch;
+ * witness_stride_bytes: any multiple of 8 that holds every frame's witness bits (it may be smaller than ceil(n/64)*8); mask_stride_bytes
+ * >= ceil(n/64)*8.  What is read and written in a row: rows of the Bloom entries, above. */
 int rbf_bloom_decode_batch(rbf_ctx *ctx, const void *filters_dev, uint64_t filter_stride_bytes,
                            const void *witnesses_dev, uint64_t witness_stride_bytes,
                            uint64_t n, uint32_t nframes, const rbf_filter_params *params,

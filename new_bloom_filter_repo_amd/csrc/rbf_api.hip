@@ -583,6 +583,10 @@ static int encode_batch_impl(rbf_ctx *ctx, const BloomBatch &b, bool outputs_zer
     if (int r = check_frame_geometry(b.n, b.nframes, b.mask_stride)) return r;
     if (int r = check_filter_strides(b.params, b.nframes, b.filter_stride)) return r;
     if (int r = check_witness_stride(b.n, b.witness_stride)) return r;
+    if (int r = check_base8(b.masks, "masks_dev")) return r;
+    if (int r = check_base8(b.filters, "filters_dev")) return r;
+    if (int r = check_base8(b.witnesses, "witnesses_dev")) return r;
+    if (int r = check_base8(b.stats, "stats_dev")) return r;
     for (uint32_t f0 = 0; f0 < b.nframes; f0 += MAX_BATCH) {
         const uint32_t cnt = std::min(b.nframes - f0, (uint32_t)MAX_BATCH);
         if (int r = encode_chunk(ctx, b.rows(f0, cnt), outputs_zeroed, ones_host ? ones_host + f0 : nullptr)) return r;
@@ -1239,6 +1243,11 @@ int rbf_encode_runs_begin_ex(rbf_ctx *ctx, const void *frames_dev, uint64_t fram
     if (filter_stride_bytes < rbf_filter_stride_min(n))
         return fail(RBF_EINVAL, "rbf_encode_runs_begin / rbf_encode_gop_begin: filter stride %llu < rbf_filter_stride_min(%llu) = %llu",
                     (unsigned long long)filter_stride_bytes, (unsigned long long)n, (unsigned long long)rbf_filter_stride_min(n));
+    if (int r = check_base8(masks_dev, "masks_dev")) return r;
+    if (int r = check_base8(ones_dev, "ones_dev")) return r;
+    if (int r = check_base8(filters_dev, "filters_dev")) return r;
+    if (int r = check_base8(witnesses_dev, "witnesses_dev")) return r;
+    if (int r = check_base8(stats_dev, "stats_dev")) return r;
     bool has_skip = false;
     if (run_starts) {
         try { ctx->run_skip.assign(pairs, 0); } catch (...) { return fail(RBF_ENOMEM, "out of host memory for %u pairs", pairs); }
@@ -1328,6 +1337,10 @@ int rbf_pack_records(rbf_ctx *ctx, uint32_t nframes, uint64_t n, const rbf_filte
     if (int r = check_frame_geometry(n, nframes, mask_stride_bytes)) return r;
     if (filter_stride_bytes % 8 || witness_stride_bytes % 8 || ((uintptr_t)record_dev % 8))
         return fail(RBF_EINVAL, "strides and the record must be 8-byte aligned");
+    if (int r = check_base8(masks_dev, "masks_dev")) return r;
+    if (int r = check_base8(filters_dev, "filters_dev")) return r;
+    if (int r = check_base8(witnesses_dev, "witnesses_dev")) return r;
+    if (int r = check_base8(stats_dev, "stats_dev")) return r;
     const uint64_t header = (uint64_t)(RECORD_HEADER_WORDS + RECORD_ROW_WORDS * (uint64_t)nframes) * 8;
     if (capacity_bytes < header || capacity_bytes % 8)
         return fail(RBF_EINVAL, "record capacity %llu is smaller than the %llu-byte header or misaligned", (unsigned long long)capacity_bytes,
@@ -1366,6 +1379,9 @@ int rbf_bloom_decode_batch(rbf_ctx *ctx, const void *filters_dev, uint64_t filte
     if (int r = check_frame_geometry(n, nframes, mask_stride_bytes)) return r;
     if (int r = check_filter_strides(params, nframes, filter_stride_bytes)) return r;
     if (witness_stride_bytes % 8) return fail(RBF_EINVAL, "witness stride must be a multiple of 8");
+    if (int r = check_base8(filters_dev, "filters_dev")) return r;
+    if (int r = check_base8(witnesses_dev, "witnesses_dev")) return r;
+    if (int r = check_base8(masks_dev, "masks_dev")) return r;
     const BloomBatch b{masks_dev, mask_stride_bytes, n, nframes, params, seeds, (void *)filters_dev, filter_stride_bytes,
                        (void *)witnesses_dev, witness_stride_bytes, nullptr};
     for (uint32_t f0 = 0; f0 < nframes; f0 += MAX_BATCH)

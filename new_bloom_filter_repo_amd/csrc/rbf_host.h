@@ -303,6 +303,13 @@ static int check_frame_geometry(uint64_t n, uint32_t nframes, uint64_t mask_stri
     return RBF_OK;
 }
 
+// A base the kernels address as 64-bit words: rows of packed bits (masks, filters, witnesses), the stats rows and the ones counts.
+static int check_base8(const void *p, const char *name)
+{
+    if ((uintptr_t)p % 8) return fail(RBF_EINVAL, "%s must be 8-byte aligned", name);
+    return RBF_OK;
+}
+
 static int check_witness_stride(uint64_t n, uint64_t witness_stride_bytes)
 {
     if (witness_stride_bytes % 8 || witness_stride_bytes < ((n + 63) / 64) * 8) return fail(RBF_EINVAL, "witness stride too small or misaligned");

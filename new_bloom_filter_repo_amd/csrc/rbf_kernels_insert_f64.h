@@ -142,7 +142,9 @@ __device__ __forceinline__ void insert_tab_steps(const uint8_t *__restrict__ mas
         pending = 0;
     };
 
-    const uint32_t nbytes32 = (uint32_t)((n + 7) >> 3), n32 = (uint32_t)n, row32 = (uint32_t)row_bytes;      // n < 2^32 (rbf_plan_batch)
+    // n < 2^32 (rbf_plan_batch).  The row pitch is the caller's and may be 2^32 or more: as the bound of a 32-bit offset it SATURATES (kept to
+    // its low 32 bits, a pitch of 2^32 staged nothing and one of 2^32 + 8 the row's first eight bytes)
+    const uint32_t nbytes32 = (uint32_t)((n + 7) >> 3), n32 = (uint32_t)n, row32 = row_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)row_bytes;
     const uint32_t gend = (uint32_t)g1;
     // my two bytes of step `s` of the chunk as 16 bits in natural order (bit j = pixel 16 * lane + j of the step)
     auto staged = [&](uint32_t s) -> uint32_t {

@@ -6,6 +6,7 @@
 //   table: "table by_class full nframes", then one line "m floor_k T" per frame
 // prints what query_table returns for that batch: nactive, the class counts (by_class = 1), the `empty` bits, with full = 1 every
 // coded entry as m:M:floor_k:T (hex), and always the 64-bit FNV-1a of the table's bytes.
+//   batch: "batch n cus flags have_ones nframes m_0 ... m_{nframes-1}": every frame its own filter size; see show_batch
 //   sweep: "sweep n nframes cus flags have_ones lo hi step [coded]" (the first `coded` frames, default all, have a filter of m bits,
 // the others none: the batch rbf_encode_gop submits for a GOP whose later pairs did not change)
 // walks m = lo, lo + step, ... up to hi and, wherever the decision differs between two samples, every m in between: one line
@@ -123,12 +124,56 @@ static int show_table(char *line)
     return 0;
 }
 
+// "batch n cus flags have_ones nframes m_0 ... m_{nframes-1}": a batch in which every frame has its own filter size (0: not coded), as
+// rbf_bloom_encode_batch / rbf_bloom_decode_batch (have_ones = 0) or rbf_encode_gop_finish (1) plan it.  Prints the undivided plan and,
+// when the batch is mixed, its two halves -- each with the conditions under which encode_chunk / decode_chunk (rbf_api.hip) run the
+// halves instead of the whole: encode_split / decode_split.  tests/test_bloom_rows_cpu.py
+static int show_batch(char *line)
+{
+    unsigned long long n;
+    unsigned cus, have_ones, nframes;
+    int flags, used = 0;
+    if (sscanf(line, "batch %llu %u %d %u %u%n", &n, &cus, &flags, &have_ones, &nframes, &used) < 5 || nframes < 1 || nframes > (unsigned)MAX_BATCH) return 2;
+    std::vector<rbf_filter_params> params(nframes), small(nframes), big(nframes);
+    char *at = line + used;
+    for (unsigned f = 0; f < nframes; ++f) {
+        char *end;
+        const unsigned long long m = strtoull(at, &end, 10);
+        if (end == at) return 2;
+        params[f] = rbf_filter_params{(uint32_t)m, 1, 0};
+        at = end;
+    }
+    Knobs k;
+    k.set_flags(flags);
+    const Plan pl = make_plan(k, cus, params.data(), nframes, n, have_ones != 0);
+    const bool mixed = split_by_family(params.data(), nframes, small.data(), big.data());
+    int encode_split = 0, decode_split = 0;
+    if (mixed && k.fp64_kernels()) {
+        const Plan ps = make_plan(k, cus, small.data(), nframes, n, false), pb = make_plan(k, cus, big.data(), nframes, n, have_ones != 0);
+        const Plan pd = make_plan(k, cus, params.data(), nframes, n, false), pbd = make_plan(k, cus, big.data(), nframes, n, false);
+        encode_split = !k.no_hash_table && pb.reads_probe_image() && pb.insert_tab && ps.nseg == pb.nseg && ps.words_per_seg == pb.words_per_seg;
+        decode_split = pbd.reads_probe_image() && ps.nseg == pd.nseg && pbd.nseg == pd.nseg && ps.words_per_seg == pd.words_per_seg &&
+                       pbd.words_per_seg == pd.words_per_seg;
+    }
+    printf("batch mixed=%d encode_split=%d decode_split=%d\n", mixed, encode_split, decode_split);
+    show("plan", pl, nframes);
+    if (mixed) {
+        show("small", make_plan(k, cus, small.data(), nframes, n, false), nframes);
+        show("big", make_plan(k, cus, big.data(), nframes, n, have_ones != 0), nframes);
+    }
+    return 0;
+}
+
 int main()
 {
-    char line[256];
+    char line[4096];
     while (fgets(line, sizeof line, stdin)) {
         if (!strncmp(line, "table", 5)) {
             if (int r = show_table(line)) return r;
+            continue;
+        }
+        if (!strncmp(line, "batch", 5)) {
+            if (int r = show_batch(line)) return r;
             continue;
         }
         if (!strncmp(line, "sweep", 5)) {
