@@ -108,35 +108,39 @@ def frame_dtype(c):
 
 
 # ---- the covering array ----------------------------------------------------------------------------------------------------------------
-def product():
-    """Every assignment of AXES, as dicts (itertools.product order)."""
-    for values in itertools.product(*[v for _, v in AXES]):
-        yield dict(zip(NAMES, values))
+def product(axes=None):
+    """Every assignment of the axes (default: AXES), as dicts (itertools.product order)."""
+    axes = AXES if axes is None else axes
+    for values in itertools.product(*[v for _, v in axes]):
+        yield dict(zip([n for n, _ in axes], values))
 
 
-def _index_table():
-    """(idx, legal mask): the full product as an (N, axes) array of value indices, and which rows are legal."""
-    sizes = [len(v) for _, v in AXES]
+def _index_table(axes=None, legal_fn=None):
+    """(idx, legal mask): the full product as an (N, axes) array of value indices, and which rows are legal.  axes, legal_fn: another
+    sweep's axes and predicate (surface_geometries.py); default: AXES and legal()."""
+    axes, legal_fn = AXES if axes is None else axes, legal if legal_fn is None else legal_fn
+    sizes = [len(v) for _, v in axes]
     idx = np.indices(sizes).reshape(len(sizes), -1).T
-    ok = np.array([legal({n: AXES[a][1][row[a]] for a, n in enumerate(NAMES)}) is None for row in idx])
+    ok = np.array([legal_fn({n: axes[a][1][row[a]] for a, (n, _) in enumerate(axes)}) is None for row in idx])
     return idx, ok
 
 
 def legal_pairs(idx):
     """{(axis a, axis b): set of (value index, value index)} over the rows of idx, a < b."""
     out = {}
-    for a, b in itertools.combinations(range(len(AXES)), 2):
+    for a, b in itertools.combinations(range(idx.shape[1]), 2):
         out[(a, b)] = {(int(x), int(y)) for x, y in np.unique(idx[:, [a, b]], axis=0)}
     return out
 
 
-def covering_array():
+def covering_array(axes=None, legal_fn=None):
     """A pairwise covering array over the legal assignments, greedily: take the legal assignment that covers the most pairs not covered
-    yet (the first of them in product order), until none is left.  Deterministic, numpy only."""
-    idx, ok = _index_table()
+    yet (the first of them in product order), until none is left.  Deterministic, numpy only.  axes, legal_fn: as for _index_table."""
+    axes = AXES if axes is None else axes
+    idx, ok = _index_table(axes, legal_fn)
     rows = idx[ok]
-    sizes = [len(v) for _, v in AXES]
-    axis_pairs = list(itertools.combinations(range(len(AXES)), 2))
+    sizes = [len(v) for _, v in axes]
+    axis_pairs = list(itertools.combinations(range(len(axes)), 2))
     codes = {(a, b): rows[:, a] * sizes[b] + rows[:, b] for a, b in axis_pairs}
     open_ = {}
     for (a, b), code in codes.items():
@@ -153,7 +157,7 @@ def covering_array():
             break
         for ab, code in codes.items():
             open_[ab][code[best]] = False
-        cases.append({n: AXES[a][1][rows[best][a]] for a, n in enumerate(NAMES)})
+        cases.append({n: axes[a][1][rows[best][a]] for a, (n, _) in enumerate(axes)})
     return cases
 
 
@@ -205,31 +209,40 @@ def clip_name(c):
 
 def clip(c):
     """The T frames of a case: a list of arrays (never written to: copy before handing them to anything that might)."""
-    from new_bloom_filter_repo_amd.synthetic import make_camera_gop, make_gop, make_panning_gop
     name = clip_name(c)
     if name not in _clips:
-        kind, noise, dt, layout, step = name
-        dtype = np.uint8 if dt == "u8" else np.uint16
-        space = "BGR" if layout == "bgr" else "YUV"
-        a, b = SEEDS[kind]
-        if kind == "static":
-            frames = (make_camera_gop(a, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
-                      + make_camera_gop(b, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
-        elif kind == "pan":
-            frames = (make_panning_gop(a, W, H, T, (2, 1), dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
-                      + make_panning_gop(b, W, H, T, (2, 1), dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
-        else:
-            frames = [f.copy() for f in make_gop(a, W, H, T, p=0.08, dtype=dtype)[:CUT] + make_gop(b, W, H, T, p=0.08, dtype=dtype)[CUT:]]
-            frames[5] = frames[4].copy()
-            frames[5][3, 7, 1] ^= 1
-        for t in range(*STEP_FRAMES):
-            frames[t] = np.clip(frames[t].astype(np.int64) + step, 0, np.iinfo(dtype).max).astype(dtype)
-        if layout == "grey":
-            frames = [np.ascontiguousarray(f[..., 0]) for f in frames]
-        for f in frames:
-            f.setflags(write=False)
-        _clips[name] = frames
+        _clips[name] = make_clip(name, W, H, SEEDS[name[0]])
     return _clips[name]
+
+
+def make_clip(name, W, H, seeds, velocities=(2, 1)):
+    """The recipe of clip() for a clip_name() tuple at W x H, with the seeds of its two scenes: the T frames, read-only.  Beyond the
+    layouts of AXES, "bgra": (H, W, 4) frames, the BGR clip with a 4th sample (s0 + s2) // 2 that changes with the scene.  velocities:
+    the camera of a "pan" clip, as make_panning_gop takes it."""
+    from new_bloom_filter_repo_amd.synthetic import make_camera_gop, make_gop, make_panning_gop
+    kind, noise, dt, layout, step = name
+    dtype = np.uint8 if dt == "u8" else np.uint16
+    space = "BGR" if layout in ("bgr", "bgra") else "YUV"
+    a, b = seeds
+    if kind == "static":
+        frames = (make_camera_gop(a, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
+                  + make_camera_gop(b, W, H, T, dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
+    elif kind == "pan":
+        frames = (make_panning_gop(a, W, H, T, velocities, dtype=dtype, color_space=space, sensor_noise=noise)[:CUT]
+                  + make_panning_gop(b, W, H, T, velocities, dtype=dtype, color_space=space, sensor_noise=noise)[CUT:])
+    else:
+        frames = [f.copy() for f in make_gop(a, W, H, T, p=0.08, dtype=dtype)[:CUT] + make_gop(b, W, H, T, p=0.08, dtype=dtype)[CUT:]]
+        frames[5] = frames[4].copy()
+        frames[5][min(3, H - 1), min(7, W - 1), 1] ^= 1
+    for t in range(*STEP_FRAMES):
+        frames[t] = np.clip(frames[t].astype(np.int64) + step, 0, np.iinfo(dtype).max).astype(dtype)
+    if layout == "grey":
+        frames = [np.ascontiguousarray(f[..., 0]) for f in frames]
+    elif layout == "bgra":
+        frames = [np.concatenate([f, ((f[..., :1].astype(np.int64) + f[..., 2:3]) // 2).astype(dtype)], axis=2) for f in frames]
+    for f in frames:
+        f.setflags(write=False)
+    return frames
 
 
 # ---- the twin's output per case, computed once --------------------------------------------------------------------------------------------

@@ -15,7 +15,10 @@ numbers are RESTATED here, so that a change of the product's composition shows a
       quality      error_bounds_ref.ROW per frame (None without quality_report): originals against decoded
 
 `mutant` names one deliberate mistake in the composition (MUTANTS); test_surface_cases_cpu.py proves that each of them changes the
-output of a case the GPU file runs -- which is how the sweep is known to fail when the product makes that mistake."""
+output of a case the GPU file runs -- which is how the sweep is known to fail when the product makes that mistake.  The last two
+are told apart by the cases of surface_geometries.py (test_surface_geometries_cpu.py): pan_rule_not_strict takes a frame of H = 2R into
+the search, which the C ABI refuses (Refused: the product would raise where the twin codes the clip unpanned), and offsets_mod_swapped
+shows only where W != H."""
 import numpy as np
 
 import error_bounds_ref as eb
@@ -30,7 +33,12 @@ DEFAULTS = dict(keyframe_interval=30, block_frames=None, mask_channels="luma", s
 IGNORED = ("gpu_lanes", "inter_frames", "gop_batching", "verify_digests")      # keywords that change no byte of what the twin predicts
 
 MUTANTS = ("hold_before_quantiser", "cuts_before_alignment", "lookahead_tolerance_not_doubled", "tolerance_from_max_bound", "no_rebase",
-           "rebase_one_frame_short", "halo_not_quantised", "digest_of_rolled_back_frame")
+           "rebase_one_frame_short", "halo_not_quantised", "digest_of_rolled_back_frame", "pan_rule_not_strict", "offsets_mod_swapped")
+GEOMETRY_MUTANTS = MUTANTS[-2:]                  # mistakes that no 96 x 64 frame shows: proven on the cases of surface_geometries.py
+
+
+class Refused(Exception):
+    """What a composition ends in when it hands a stage what include/rbf.h says the stage refuses (RBF_EINVAL): no output at all."""
 
 
 def options(keywords):
@@ -123,7 +131,9 @@ def block(seg, run_starts, o, mutant=None):
     starts, R = sorted(int(t) for t in run_starts), int(o["pan_range"])
     # 2. pan
     S, offs, adopted = [f.copy() for f in x], [(0, 0)] * F, []
-    panned = bool(R) and W > 2 * R and H > 2 * R
+    panned = bool(R) and (W >= 2 * R and H >= 2 * R if mutant == "pan_rule_not_strict" else W > 2 * R and H > 2 * R)
+    if panned and not (W > 2 * R and H > 2 * R):
+        raise Refused("rbf_pan_search: width or height <= 2*range")      # (pan_rule_not_strict: where the search has no grid point)
     if panned:
         S, offs, adopted, _ = pan_ref.stabilise(x, R, tol, starts)
         offs = [(int(ox), int(oy)) for ox, oy in offs]
@@ -144,7 +154,8 @@ def block(seg, run_starts, o, mutant=None):
                         end = max(j + 1, end - 1)
                     for f in range(j, end):
                         S[f] = pan_ref.roll(S[f], -cx, -cy)
-                        offs[f] = ((old[f][0] - cx) % W, (old[f][1] - cy) % H)
+                        mx, my = (H, W) if mutant == "offsets_mod_swapped" else (W, H)
+                        offs[f] = ((old[f][0] - cx) % mx, (old[f][1] - cy) % my)
             adopted = [row for row in adopted if row[0] not in cuts]
     # 4. bounded keyframes, 5. the hold
     S = np.stack(S)

@@ -5,15 +5,12 @@ offsets, every decoded frame, the digests, the quality report.  No tolerance any
 not the assertion.  test_surface_cases_cpu.py proves that the cases exercise what they turn on and that a composition with a stage
 misplaced or a tolerance wrong changes the twin's output on one of them, so it fails here.  Then the invariants the twin has, on a
 subset with every near-lossless mode and both sample types: encoder knobs, shards, decoder routes."""
-import numpy as np
 import pytest
 
 import surface_cases as sc
-import surface_twin as st
+import surface_run
 from new_bloom_filter_repo_amd import container
-from new_bloom_filter_repo_amd.integrity import build_trailer
-from new_bloom_filter_repo_amd.verify import verify_max_error
-from new_bloom_filter_repo_amd.video_compressor import ImprovedVideoCompressor
+from surface_run import decode, same_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -22,47 +19,8 @@ _runs = {}
 
 
 def encode(c):
-    """The container of case c as [(type, record)] -- frame records, then the pan table and the digest trailer as compress_video
-    appends them -- and what the call left behind."""
-    frames = [f.copy() for f in sc.clip(c)]
-    with ImprovedVideoCompressor(**sc.keywords(c)) as comp:
-        if sc.shards(c) is None:
-            comp.compress_video(frames, input_color_space=sc.color_space(c))
-            records = list(comp.last_compressed_frames)
-            out = dict(scene_cuts=list(comp.last_scene_cuts), pans=list(comp.last_pans), pan_offsets=dict(comp.last_pan_offsets),
-                       digests=comp.last_digests, quality=comp.last_quality)
-        else:
-            if sc.color_space(c) == "YUV":       # what compress_video does to YUV input before it plans the ranges
-                frames = [comp.compressor.add_yuv_info_to_frame(f) for f in frames]
-            records, out = [], dict(scene_cuts=[], pans=[], pan_offsets={}, digests=[], quality=[])
-            for start, stop in sc.shards(c):
-                first = start if start % I == 0 else start - 1
-                records += comp.encode_range(frames[first:], first, start, stop)
-                out["scene_cuts"] += comp.last_scene_cuts
-                out["pans"] += comp.last_pans
-                out["pan_offsets"].update({start + k: v for k, v in comp.last_pan_offsets.items()})
-                out["digests"] = None if comp.last_digests is None else out["digests"] + comp.last_digests
-                out["quality"] = None if comp.last_quality is None else out["quality"] + comp.last_quality
-            if out["pan_offsets"]:
-                records.append((container.PANS, container.build_pans(out["pan_offsets"])))
-            if out["digests"] is not None:
-                records.append((container.DIGESTS, build_trailer(out["digests"])))
-    out["records"] = records
-    return out
-
-
-def decode(records, **how):
-    """The frames a fresh default compressor rebuilds from the written and parsed container, and its last_integrity.  how:
-    constructor keywords of the decoder, and chain_chunk_frames."""
-    chunk = how.pop("chain_chunk_frames", None)
-    fresh = ImprovedVideoCompressor(**how)
-    if chunk:
-        fresh.chain_chunk_frames = chunk
-    try:
-        dec = fresh.decompress_video(compressed_frames=container.parse(container.write(records)))
-        return [np.asarray(getattr(d, "data", d)) for d in dec], fresh.last_integrity
-    finally:
-        fresh.close()
+    """surface_run.encode of case c: its container as [(type, record)] and what the call left behind."""
+    return surface_run.encode(sc.clip(c), sc.keywords(c), sc.color_space(c), sc.shards(c))
 
 
 def run(k):
@@ -73,39 +31,10 @@ def run(k):
     return _runs[k]
 
 
-def same_frames(a, b):
-    return len(a) == len(b) and all(x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("k", range(len(sc.CASES)), ids=sc.IDS)
 def test_the_surface_is_its_twin(k):
-    c, tw, got = sc.CASES[k], sc.twin_of(k), run(k)
-    x = sc.clip(c)
-    assert [ty for ty, _ in got["records"]] == tw["kinds"]
-    assert got["scene_cuts"] == tw["scene_cuts"]
-    assert [tuple(int(v) for v in row) for row in got["pans"]] == tw["pans"]
-    assert {int(i): (int(o[0]), int(o[1])) for i, o in got["pan_offsets"].items()} == tw["pan_offsets"]
-    bad = [t for t, (a, b) in enumerate(zip(got["decoded"], tw["decoded"])) if a.shape != b.shape or a.dtype != b.dtype or not np.array_equal(a, b)]
-    assert len(got["decoded"]) == T and not bad, bad
-    if c["frame_digests"]:
-        assert [int(d) for d in got["digests"]] == tw["digests"]
-        assert got["integrity"]["frames"] == got["integrity"]["checked"] == T
-    else:
-        assert got["digests"] is None and got["integrity"]["checked"] == 0
-    if c["quality_report"]:
-        rows = tw["quality"]
-        assert [(q["max_abs_error"], q["changed_samples"], q["over_bound"]) for q in got["quality"]] == \
-               [(int(r["max_abs"]), int(r["differing"]), int(r["over_bound"])) for r in rows]
-        samples = x[0].size
-        assert [q["mse"] for q in got["quality"]] == [int(r["sse"]) / samples for r in rows]
-    else:
-        assert got["quality"] is None
-    if c["near"] == "off":
-        assert same_frames(got["decoded"], x)
-    else:
-        kw = sc.keywords(c)
-        v = verify_max_error(list(x), got["decoded"], kw["max_error"] if "max_error" in kw else kw["error_bounds"])
-        assert v["within_bound"] and v["frame_count"] == T, v
+    c = sc.CASES[k]
+    surface_run.assert_is_twin(run(k), sc.twin_of(k), sc.clip(c), sc.keywords(c))
 
 
 SUBSET = sc.invariance_cases()

@@ -196,7 +196,7 @@ def _same(a, b):
     return all(np.array_equal(u, v) for u, v in zip(a["decoded"], b["decoded"]))
 
 
-@pytest.mark.parametrize("mutant", st.MUTANTS)
+@pytest.mark.parametrize("mutant", [m for m in st.MUTANTS if m not in st.GEOMETRY_MUTANTS])      # (those: test_surface_geometries_cpu.py)
 def test_the_cases_tell_the_mutant_from_the_twin(mutant):
     caught = [sc.IDS[k] for k in range(len(sc.CASES)) if not _same(sc.twin_of(k), sc.twin_of(k, mutant))]
     assert caught, mutant
