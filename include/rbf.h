@@ -682,6 +682,40 @@ int rbf_pan_search(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_b
 int rbf_roll_frames(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
                     uint32_t width, uint32_t height, uint32_t pixel_bytes, const int32_t *offsets);
 
+/* ---- views: a region of a frame, reduced by a box mean (no reference counterpart) ---------------------------------------------- */
+/* A reader that wants part of a clip -- a frame range, a region, a reduced preview -- takes it where the rebuilt frames lie, so that
+ * only the view crosses to the host.  A VIEW of a dense (H, W, C) frame of B-bit samples is given by a region (x0, y0, w, h) and a
+ * scale s in {1, 2, 4, 8}:
+ *     region     w, h >= 1, x0 + w <= W, y0 + h <= H.
+ *     output     dense (ceil(h/s), ceil(w/s), C), of the same sample type.
+ *     blocks     output pixel (Y, X) covers the source pixels x0 + sX .. min(x0 + sX + s, x0 + w) - 1 by
+ *                y0 + sY .. min(y0 + sY + s, y0 + h) - 1: the block grid hangs off the region's corner, and a ragged last block
+ *                averages over the cnt pixels it has.
+ *     rule       per channel, out = floor((2*sum + cnt) / (2*cnt)) with sum the sum of the block's cnt samples of that channel.  For
+ *                a full block that is (sum + s*s/2) >> 2*log2(s); with s = 1 it is a plain crop.
+ * All values are integers and the rule rounds half up (a 2x2 block that sums to 4q + 2 gives q + 1, one that sums to 4q + 1 gives q).
+ * The largest numerator is 2*64*65535 + 64: 32 bits are enough.  No other filter: a box mean, nothing is interpolated.
+ *
+ * rbf_frame_view_batch: the views of `count` frames of a resident block, written back to back at out_dev (view j at out_dev +
+ * j * ceil(h/s)*ceil(w/s)*channels*sample_bytes).  frame_index (HOST, count entries, ascending): frame i lies at frames_dev +
+ * i*frame_stride_bytes -- the slot addressing of a chain block, the convention of rbf_rice_encode_intra_near; every offset is formed in
+ * 64 bits.  Read-only on the frames; asynchronous on the context's stream.  Where every source row the region touches starts on a
+ * 16-byte boundary (frames_dev, frame_stride_bytes, width*channels*sample_bytes and x0*channels*sample_bytes multiples of 16) the full
+ * blocks go through 16-byte loads in whole lane tiles of 16 / gcd(16, s*channels*sample_bytes) output pixels; what that leaves -- the
+ * columns behind the last whole tile, the ragged last rows -- and the whole view of tiny frames and of every other layout go through a
+ * kernel with one lane per output sample, launched over those output pixels only.  Not timed: there is no RBF_K_ id for it, as for
+ * rbf_cut_stats.
+ * count == 0: RBF_OK, nothing is launched.  RBF_EINVAL, before anything is launched and with out_dev untouched: a scale outside
+ * {1, 2, 4, 8}, an empty region or one that leaves the frame, channels outside 1..4, sample_bytes not 1 or 2, a null pointer, a base or
+ * stride that is not a multiple of sample_bytes, frame_stride_bytes < width*height*channels*sample_bytes, indices that do not ascend,
+ * capacity_bytes smaller than the count views, out_dev's range overlapping the source span [frames_dev, frames_dev +
+ * last index * frame_stride_bytes + a frame). */
+int rbf_frame_view_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                         const uint32_t *frame_index, uint32_t count,
+                         uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                         uint32_t x0, uint32_t y0, uint32_t roi_w, uint32_t roi_h, uint32_t scale,
+                         void *out_dev, uint64_t capacity_bytes);
+
 #ifdef __cplusplus
 }
 #endif

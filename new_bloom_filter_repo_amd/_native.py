@@ -112,6 +112,7 @@ _PROTOS = {
     "rbf_error_stats": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
     "rbf_pan_search": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "rbf_roll_frames": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _i32p]),
+    "rbf_frame_view_batch": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u32), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64]),
     "rbf_frame_digest_batch": (_int, [_vp, _vp, _u64, _u32, _u64, _vp]),
     "rbf_frame_digest_host": (_u64, [_vp, _u64]),
 }

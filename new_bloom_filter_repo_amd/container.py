@@ -242,6 +242,43 @@ def inter_runs(types):
     return runs
 
 
+def read_span(types, start=0, stop=None, step=1):
+    """What a reader of the frames range(start, stop, step) of a checked stream has to decode, from the record types alone: (keys, runs).
+    keys: the keyframe records that are wanted themselves, ascending (lone keyframes and keyframes in front of a run alike).  runs:
+    [(keyframe record, first record, end, positions)] for every run of inter_runs(types) that holds a wanted frame -- `end` is one past
+    the LAST record the reader needs, not the run's end, and positions are the wanted records as offsets from the run's first record.
+    Runs and keyframes without a wanted frame do not appear.  stop None or past the end: the end of the stream.  ValueError for
+    step < 1, start < 0, or a span that is empty after clamping."""
+    count = len(types)
+    for name, v in (("start", start), ("step", step)) + ((("stop", stop),) if stop is not None else ()):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    start, step = int(start), int(step)
+    stop = count if stop is None else min(int(stop), count)
+    if step < 1:
+        raise ValueError("step must be >= 1, got %d" % step)
+    if start < 0:
+        raise ValueError("start must be >= 0, got %d" % start)
+    if start >= stop:
+        raise ValueError("no frame in [%d, %d) of a stream of %d frames" % (start, stop, count))
+    wanted = range(start, stop, step)
+    keys = [i for i in wanted if types[i] in KEY_TYPES]
+    runs = []
+    for k, lo, hi in inter_runs(types):
+        first = start if start >= lo else lo + (start - lo) % step           # the first wanted record at or behind lo
+        inside = list(range(first, min(hi, stop), step))
+        if inside:
+            runs.append((k, lo, inside[-1] + 1, [i - lo for i in inside]))
+    return keys, runs
+
+
+def span_records(keys, runs):
+    """How many records a reader of read_span's (keys, runs) decodes: every run's keyframe and its records up to the last one needed,
+    and the wanted keyframes that front no such run."""
+    fronts = {k for k, _, _, _ in runs}
+    return len(fronts | set(keys)) + sum(end - lo for _, lo, end, _ in runs)
+
+
 def is_keyframe(t, first_index, keyframe_interval, inter_frames=True):
     """The keyframe rule for global frame t of a call whose first frame is global frame first_index: t % keyframe_interval == 0, or no
     inter-frames at all, or the frame's predecessor is not among the frames handed in."""

@@ -21,6 +21,7 @@
 #include "rbf_kernels_cut.h"
 #include "rbf_kernels_error.h"
 #include "rbf_kernels_pan.h"
+#include "rbf_kernels_view.h"
 #include "rbf_rice_host.h"
 #include "rbf_kernels_keyquant.h"
 
@@ -1930,6 +1931,89 @@ int rbf_roll_frames(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes,
             if (int r = flush()) return r;
     }
     return flush();
+}
+
+// ---- views: a region of the listed frames of a resident block, reduced by a box mean (rbf_view.h, rbf_kernels_view.h); read-only on
+// the frames, nothing is written by a call that is refused
+int rbf_frame_view_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes,
+                         const uint32_t *frame_index, uint32_t count,
+                         uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                         uint32_t x0, uint32_t y0, uint32_t roi_w, uint32_t roi_h, uint32_t scale,
+                         void *out_dev, uint64_t capacity_bytes)
+{
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    if (int r = check_layout(l, count, rules)) return r;
+    if (!view_scale_ok(scale)) return fail(RBF_EINVAL, "scale must be 1, 2, 4 or 8, got %u", scale);
+    if (roi_w == 0 || roi_h == 0) return fail(RBF_EINVAL, "empty region %ux%u", roi_w, roi_h);
+    if ((uint64_t)x0 + roi_w > width || (uint64_t)y0 + roi_h > height)
+        return fail(RBF_EINVAL, "region %ux%u at (%u, %u) leaves a frame of %ux%u", roi_w, roi_h, x0, y0, width, height);
+    if (count == 0) return RBF_OK;
+    if (!frames_dev || !frame_index || !out_dev) return fail(RBF_EINVAL, "null pointer");
+    if ((uintptr_t)frames_dev % sample_bytes || (uintptr_t)out_dev % sample_bytes)
+        return fail(RBF_EINVAL, "frames or views misaligned for %u-byte samples", sample_bytes);
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (frame_bytes / pixel != n || frame_bytes >> 48) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    if ((uint64_t)width * pixel > 0x7FFFFFFFull) return fail(RBF_ERANGE, "a row of %llu bytes is too long", (unsigned long long)width * pixel);
+    if (frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    for (uint32_t i = 1; i < count; ++i)
+        if (frame_index[i] <= frame_index[i - 1])                 // (a frame listed twice would be viewed twice: ask for it once)
+            return fail(RBF_EINVAL, "frame indices must ascend: %u after %u", frame_index[i], frame_index[i - 1]);
+    const uint32_t last = frame_index[count - 1];
+    if (frame_stride_bytes >> 48 || (uint64_t)last * frame_stride_bytes >> 62) return fail(RBF_ERANGE, "frame %u at stride %llu is out of reach", last, (unsigned long long)frame_stride_bytes);
+    const bool aligned16 = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
+    const ViewPlan p = view_plan(width, pixel, x0, roi_w, roi_h, scale, aligned16);
+    const uint64_t view_bytes = (uint64_t)p.out_w * p.out_h * pixel, need = view_bytes * count;
+    if (capacity_bytes < need)
+        return fail(RBF_EINVAL, "%u views of %llu bytes need %llu bytes, capacity is %llu", count, (unsigned long long)view_bytes, (unsigned long long)need,
+                    (unsigned long long)capacity_bytes);
+    const uintptr_t src_lo = (uintptr_t)frames_dev, src_hi = src_lo + (uint64_t)last * frame_stride_bytes + frame_bytes;      // the source span
+    const uintptr_t out_lo = (uintptr_t)out_dev, out_hi = out_lo + need;
+    if (out_lo < src_hi && src_lo < out_hi) return fail(RBF_EINVAL, "out_dev lies inside the source span: a view is never written over the frames");
+    // what the wide kernel leaves: the columns behind its last whole tile (beside its rows), and the rows below them (whole rows)
+    const uint32_t rects[2][4] = {{p.wide_cols, 0, p.out_w - p.wide_cols, p.wide_rows}, {0, p.wide_rows, p.out_w, p.out_h - p.wide_rows}};
+    const uint64_t wide_lanes = (uint64_t)p.tiles_x * p.wide_rows, bx_wide = (wide_lanes + WG_THREADS - 1) / WG_THREADS;
+    uint64_t bx_px[2];
+    for (int r = 0; r < 2; ++r) bx_px[r] = ((uint64_t)rects[r][2] * rects[r][3] * channels + WG_THREADS - 1) / WG_THREADS;
+    if (bx_wide > 0x7FFFFFFFull || bx_px[0] > 0x7FFFFFFFull || bx_px[1] > 0x7FFFFFFFull)
+        return fail(RBF_ERANGE, "view of %ux%u pixels is too large", p.out_w, p.out_h);
+    if (int r = ctx->view_index.reserve((size_t)count * 4)) return r;
+    HIP_TRY(hipMemcpyAsync(ctx->view_index.p, frame_index, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));      // (pageable: staged before the call returns)
+    const uint8_t *const frames = (const uint8_t *)frames_dev;
+    const uint32_t row_bytes = (uint32_t)(width * pixel), out_row_bytes = p.out_w * pixel;
+    const uint64_t roi_off = ((uint64_t)y0 * width + x0) * pixel;
+    constexpr uint32_t MAX_Y = 65535;                             // frames of one launch (gridDim.y)
+    for (uint32_t f0 = 0; f0 < count; f0 += MAX_Y) {
+        const uint32_t cnt = count - f0 < MAX_Y ? count - f0 : MAX_Y;
+        const uint32_t *const index = ctx->view_index.p + f0;
+        uint8_t *const out = (uint8_t *)out_dev + (uint64_t)f0 * view_bytes;
+        if (bx_wide) {
+            const dim3 grid((uint32_t)bx_wide, cnt), block(WG_THREADS);
+#define RBF_VIEW(S, C, K) hipLaunchKernelGGL((k_frame_view<S, C, K>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, index, row_bytes, roi_off, p.tiles_x, p.wide_rows, out, view_bytes, out_row_bytes)
+#define RBF_VIEW_C(S, K) do { if (channels == 1) RBF_VIEW(S, 1, K); else if (channels == 2) RBF_VIEW(S, 2, K); else if (channels == 3) RBF_VIEW(S, 3, K); else RBF_VIEW(S, 4, K); } while (0)
+#define RBF_VIEW_S(S) do { if (scale == 1) RBF_VIEW_C(S, 1); else if (scale == 2) RBF_VIEW_C(S, 2); else if (scale == 4) RBF_VIEW_C(S, 4); else RBF_VIEW_C(S, 8); } while (0)
+            if (sample_bytes == 1) RBF_VIEW_S(uint8_t); else RBF_VIEW_S(uint16_t);
+#undef RBF_VIEW_S
+#undef RBF_VIEW_C
+#undef RBF_VIEW
+        }
+        for (int r = 0; r < 2; ++r) {
+            if (!bx_px[r]) continue;
+            const uint32_t *const q = rects[r];
+            const dim3 grid((uint32_t)bx_px[r], cnt), block(WG_THREADS);
+#define RBF_VIEW_PX(S, K) hipLaunchKernelGGL((k_frame_view_px<S, K>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, index, width, channels, x0, y0, roi_w, roi_h, p.out_w, q[0], q[1], q[2], q[3], out, view_bytes)
+#define RBF_VIEW_PX_S(S) do { if (scale == 1) RBF_VIEW_PX(S, 1); else if (scale == 2) RBF_VIEW_PX(S, 2); else if (scale == 4) RBF_VIEW_PX(S, 4); else RBF_VIEW_PX(S, 8); } while (0)
+            if (sample_bytes == 1) RBF_VIEW_PX_S(uint8_t); else RBF_VIEW_PX_S(uint16_t);
+#undef RBF_VIEW_PX_S
+#undef RBF_VIEW_PX
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return RBF_OK;
 }
 
 // ---- integrity: FD1 frame digests (rbf_digest.h, rbf_kernels_digest.h)

@@ -125,6 +125,7 @@ struct rbf_ctx {
         int reserve_rows(size_t n) { try { if (rows.size() < n) rows.resize(n); } catch (...) { return fail(RBF_ENOMEM, "out of host memory"); } return RBF_OK; }
     } pan_host;
     DevBuf<uint8_t> roll_scratch;    // rbf_roll_frames: where a chunk of up to eight frames is rolled to before it is copied back
+    DevBuf<uint32_t> view_index;     // rbf_frame_view_batch (rbf_kernels_view.h): the call's frame indices
     struct SharedHashTable *hash_shared = nullptr;               // the pixel-index hash table this context holds a reference to
     uint4 *hash_tab = nullptr;                                    // = hash_shared->table
     // host staging of encode_gop: device-visible pinned block [flag | ones...] the GPU publishes into

@@ -343,20 +343,36 @@ def gather_values(ctx, frame, mask_packed):
     return vals
 
 
-def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt=None, before_download=None):
+class DeviceFrame:
+    """A frame that lies in device memory (a type-3 / type-7 keyframe where SampleCoder decoded it): what rebuild_chain needs of a base
+    it copies into its block device to device instead of uploading it."""
+
+    def __init__(self, ptr, shape, dtype):
+        self.ptr, self.shape, self.dtype = ptr, tuple(shape), np.dtype(dtype)
+        self.ndim = len(self.shape)
+        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
+
+
+def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt=None, before_download=None, view=None):
     """The chunked device-side rebuild of a run of inter-frames after `base` that both record types share (apply_chain below, SampleCoder.
     apply_chain).  The run is rebuilt in chunks of at most `chunk_frames` frames and `chunk_bytes` bytes (1080p YUV444: 41 frames; an 8K
     16-bit frame: one at a time -- device block and host block stay bounded whatever the frame size): one upload of the chunk's predecessor
     into slot 0 of a block of frames `fb`, one of its masks as padded rows `mb`, then rebuild(c0, cnt, fb, mb) has the device write frames
     c0 .. c0+cnt-1 of the run into slots 1 .. cnt, no host round trip in between; the chunk's frames come back in ONE download.
-    alloc(name, nbytes): the device blocks.  on_rebuilt(ptr, frame_bytes, count), optional: called after rebuild(...) and before the chunk's
+    alloc(name, nbytes): the device blocks.  base: the frame in front of the run, an array or a DeviceFrame of the same context (copied
+    into slot 0 device to device).  on_rebuilt(ptr, frame_bytes, count), optional: called after rebuild(...) and before the chunk's
     download with the device address of the chunk's `count` rebuilt frames, frame_bytes apart -- where the frame digests of a container
     with a trailer are taken (integrity.py), from bytes the scatter has just written.  before_download(fb, c0, count), optional: called
     after that hook, for a caller that changes the chunk's frames on the device before they come back (a panned run is rolled back here:
     video_compressor._decode_run).  The next chunk still has to see the frame the device REBUILT as its predecessor, not what was
     downloaded: a hook that returns True has put that frame into slot 0 itself (device to device, before it changed slot `count`), and
     the next chunk's upload of its predecessor is skipped.  Returns the list of frames.  They are VIEWS of the
-    downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
+    downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive.
+    view, optional (view.View): the hook order per chunk is on_rebuilt (digests of the full frames), before_download, then the view --
+    rbf_frame_view_batch over the chunk's wanted frames (view.wanted: positions in the run, None = all) into a view block, and only that
+    block is downloaded; a chunk with no wanted frame downloads nothing.  The full frames never reach the host, so the chain keeps slot
+    0 resident itself: unless before_download has done so, the chunk's last frame is copied into slot 0 device to device, and the
+    predecessor is never uploaded again.  Returns the views of the wanted frames, in order."""
     H, W, _, _ = nat.frame_geometry(base)
     n = H * W
     stride = nat.packed_stride(n)
@@ -368,7 +384,17 @@ def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild,
     per = max(1, min(int(chunk_frames), total, int(chunk_bytes) // max(1, fbytes)))
     fb = alloc("chain", (per + 1) * fbytes)                       # slot 0: the predecessor of the chunk's first frame
     mb = alloc("masks", per * stride)
-    prev, resident = base, False                                  # resident: slot 0 already holds the chunk's predecessor
+    on_device = isinstance(base, DeviceFrame)
+    if on_device:
+        nat.check(nat.lib().rbf_memcpy_d2d(fb.ctx.handle, fb.ptr, base.ptr, fbytes))
+    wanted = None
+    if view is not None:
+        from .view import views_device
+        wanted = list(range(total)) if view.wanted is None else [p for p in view.wanted if 0 <= p < total]
+        most = max([sum(1 for p in wanted if c0 <= p < c0 + per) for c0 in range(0, total, per)])
+        vbytes = int(np.prod(view.shape(base.shape))) * base.dtype.itemsize
+        vblock = alloc("views", max(8, most * vbytes))            # one view block for the fullest chunk
+    prev, resident = base, on_device                              # resident: slot 0 already holds the chunk's predecessor
     for c0 in range(0, total, per):
         cnt = min(per, total - c0)
         if not resident:
@@ -378,35 +404,45 @@ def rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild,
         if on_rebuilt is not None:
             on_rebuilt(fb.ptr + fbytes, fbytes, cnt)
         resident = bool(before_download(fb, c0, cnt)) if before_download is not None else False
+        if view is not None:
+            if not resident and c0 + cnt < total:                 # the next chunk's predecessor stays where it was rebuilt
+                nat.check(nat.lib().rbf_memcpy_d2d(fb.ctx.handle, fb.ptr, fb.ptr + cnt * fbytes, fbytes))
+            resident = True
+            slots = [p - c0 + 1 for p in wanted if c0 <= p < c0 + cnt]
+            if slots:
+                out += list(views_device(fb.ctx, lambda name, nbytes: vblock, fb.ptr, fbytes, slots, base.shape, base.dtype, view))
+            continue
         block = fb.download(cnt * fbytes, offset=fbytes).view(base.dtype).reshape((cnt,) + base.shape)
         out += [block[j] for j in range(cnt)]
         prev = block[cnt - 1]
     return out
 
 
-def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None):
+def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None, view=None):
     """A8 for a run of inter-frames: frame t = frame t-1 with `values_list[t]` written at mask t's '1' pixels
     (improved_video_compressor.py:849-909), rebuilt ON THE DEVICE in chunks (rebuild_chain): one upload of the chunk's values, then per
-    frame a device-to-device copy of its predecessor and one scatter.  on_rebuilt, before_download: rebuild_chain's hooks.
+    frame a device-to-device copy of its predecessor and one scatter.  on_rebuilt, before_download, view: rebuild_chain's hooks and view;
+    base may be a DeviceFrame of ctx.
     Returns the list of frames.  They are VIEWS of the downloaded chunk blocks: keeping one of them alive keeps its whole chunk alive."""
-    base = np.ascontiguousarray(base)
+    if not isinstance(base, DeviceFrame):
+        base = np.ascontiguousarray(base)
     H, W, C, sb = nat.frame_geometry(base)
     stride = nat.packed_stride(H * W)
     fbytes = base.nbytes
     L = nat.lib()
-    bufs = []
+    bufs, named = [], {}
 
     def alloc(name, nbytes):
         bufs.append(ctx.alloc(nbytes))
         return bufs[-1]
 
     def rebuild(c0, cnt, fb, mb):
-        if len(bufs) == 2:                                        # the first chunk is a full one: one value block for the largest chunk
+        if "values" not in named:                                 # the first chunk is a full one: one value block for the largest chunk
             vcap = 8
             for c in range(0, len(masks_packed), cnt):
                 vcap = max(vcap, sum(np.asarray(v).nbytes for v in values_list[c:c + cnt]))
-            alloc("values", vcap)
-        vb = bufs[2]
+            named["values"] = alloc("values", vcap)
+        vb = named["values"]
         vals, offs = [], []
         off = 0
         for j in range(cnt):
@@ -420,7 +456,7 @@ def apply_chain(ctx, base, masks_packed, values_list, chunk_frames=64, chunk_byt
             dst = fb.ptr + (j + 1) * fbytes
             nat.check(L.rbf_memcpy_d2d(ctx.handle, dst, fb.ptr + j * fbytes, fbytes))
             nat.check(L.rbf_scatter_values(ctx.handle, dst, W, H, W * C * sb, C * sb, sb, C, mb.ptr + j * stride, vb.ptr + offs[j]))
-    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download)
+    out = rebuild_chain(alloc, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download, view)
     for b in bufs:
         b.free()
     return out

@@ -23,7 +23,8 @@ import numpy as np
 
 from . import _native as nat
 from .container import INTER_RICE, KEY_NEAR, KEY_RICE  # noqa: F401  (the record types this module's streams travel in)
-from .engine import rebuild_chain
+from .engine import DeviceFrame, rebuild_chain
+from .view import views_device
 from .frame_codec import YUVFrame, _PlaneDict, frame_data
 
 CHUNK = 1024
@@ -222,42 +223,54 @@ class SampleCoder:
         mb = self._buf("pair_mask", stride).upload(nat.mask_rows([mask_packed], H * W))
         return self.encode_inter(fb.ptr, a.nbytes, 2, W, H, C, sb, mb.ptr, stride, [ones])[0]
 
-    def decode_frame(self, stream, height, width, channels, itemsize, on_decoded=None):
+    def decode_frame_device(self, stream, height, width, channels, itemsize, bounds=None, on_decoded=None):
+        """A type-3 stream (bounds: a type-7 stream and its per-channel bounds) decoded into the coder's frame block, where it stays: a
+        DeviceFrame -- (H, W) for channels == 0, else (H, W, channels) -- that is valid until this coder decodes its next frame.  Nothing
+        is downloaded.  on_decoded(ptr, frame_bytes, 1), optional: called with the frame's device address (engine.rebuild_chain's hook)."""
+        C = max(1, channels)
+        nbytes = height * width * C * itemsize
+        fb = self._buf("frame", nbytes)
+        src = np.frombuffer(stream, dtype=np.uint8)
+        if bounds is None:
+            nat.check(nat.lib().rbf_rice_decode_intra(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, fb.ptr))
+        else:
+            d = (ctypes.c_uint32 * C)(*_near_bounds(bounds, C))
+            try:
+                nat.check(nat.lib().rbf_rice_decode_intra_near(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, d, fb.ptr))
+            except nat.RbfError as e:
+                if e.code != nat.RBF_EINVAL:
+                    raise
+                raise ValueError("corrupt bounded keyframe record: %s" % e) from None      # (the record's bytes are wrong, not the call)
+        if on_decoded is not None:
+            on_decoded(fb.ptr, nbytes, 1)
+        return DeviceFrame(fb.ptr, (height, width) if channels == 0 else (height, width, C), np.uint8 if itemsize == 1 else np.uint16)
+
+    def fetch(self, frame, view=None):
+        """A DeviceFrame of this coder's context on the host: the whole frame, or with view (view.View) its view only
+        (rbf_frame_view_batch into a view block, one download of exactly the view)."""
+        if view is None:
+            out = np.empty(frame.nbytes, dtype=np.uint8)
+            nat.check(nat.lib().rbf_memcpy_d2h(self.ctx.handle, out.ctypes.data, frame.ptr, frame.nbytes))
+            return out.view(frame.dtype).reshape(frame.shape)
+        return views_device(self.ctx, self._buf, frame.ptr, frame.nbytes, [0], frame.shape, frame.dtype, view)[0]
+
+    def decode_frame(self, stream, height, width, channels, itemsize, on_decoded=None, view=None):
         """A type-3 stream back to its frame: (H, W) for channels == 0, else (H, W, channels) (rbf_rice_decode_intra).
-        on_decoded(ptr, frame_bytes, 1), optional: called with the frame's device address before its download (engine.rebuild_chain's hook)."""
-        C = max(1, channels)
-        nbytes = height * width * C * itemsize
-        fb = self._buf("frame", nbytes)
-        src = np.frombuffer(stream, dtype=np.uint8)
-        nat.check(nat.lib().rbf_rice_decode_intra(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, fb.ptr))
-        if on_decoded is not None:
-            on_decoded(fb.ptr, nbytes, 1)
-        out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
-        return out.reshape((height, width) if channels == 0 else (height, width, C))
+        on_decoded(ptr, frame_bytes, 1), optional: called with the frame's device address before its download (engine.rebuild_chain's hook).
+        view, optional (view.View): the hook first, then the view on the device, then a download of the view only."""
+        return self.fetch(self.decode_frame_device(stream, height, width, channels, itemsize, None, on_decoded), view)
 
-    def decode_near_frame(self, stream, height, width, channels, itemsize, bounds, on_decoded=None):
+    def decode_near_frame(self, stream, height, width, channels, itemsize, bounds, on_decoded=None, view=None):
         """decode_frame for a type-7 stream: the rebuilt frame Y (rbf_rice_decode_intra_near); bounds: the record's per-channel bounds."""
-        C = max(1, channels)
-        nbytes = height * width * C * itemsize
-        fb = self._buf("frame", nbytes)
-        src = np.frombuffer(stream, dtype=np.uint8)
-        d = (ctypes.c_uint32 * C)(*_near_bounds(bounds, C))
-        try:
-            nat.check(nat.lib().rbf_rice_decode_intra_near(self.ctx.handle, src.ctypes.data, src.nbytes, width, height, C, itemsize, d, fb.ptr))
-        except nat.RbfError as e:
-            if e.code != nat.RBF_EINVAL:
-                raise
-            raise ValueError("corrupt bounded keyframe record: %s" % e) from None      # (the record's bytes are wrong, not the call)
-        if on_decoded is not None:
-            on_decoded(fb.ptr, nbytes, 1)
-        out = fb.download(nbytes).view(np.uint8 if itemsize == 1 else np.uint16)
-        return out.reshape((height, width) if channels == 0 else (height, width, C))
+        return self.fetch(self.decode_frame_device(stream, height, width, channels, itemsize, bounds, on_decoded), view)
 
-    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None):
+    def apply_chain(self, base, masks_packed, streams, chunk_frames=64, chunk_bytes=256 << 20, on_rebuilt=None, before_download=None, view=None):
         """engine.apply_chain for type-4 records: frame t = frame t-1 plus the residuals of stream t at mask t's '1' pixels, rebuilt on the
         device in chunks of frames (one upload of the chunk's masks and streams, ONE rbf_rice_apply_inter, one download).  on_rebuilt,
-        before_download: rebuild_chain's hooks.  Returns the frames as views of the downloaded chunk blocks."""
-        base = np.ascontiguousarray(base)
+        before_download, view: rebuild_chain's hooks and view; base may be a DeviceFrame of this coder's context.  Returns the frames as
+        views of the downloaded chunk blocks (with view: the views of the wanted frames)."""
+        if not isinstance(base, DeviceFrame):
+            base = np.ascontiguousarray(base)
         H, W, C, sb = nat.frame_geometry(base)
         stride = nat.packed_stride(H * W)
 
@@ -266,4 +279,4 @@ class SampleCoder:
             blob = np.frombuffer(b"".join(part), dtype=np.uint8)
             sizes = (ctypes.c_uint64 * cnt)(*[len(s) for s in part])
             nat.check(nat.lib().rbf_rice_apply_inter(self.ctx.handle, blob.ctypes.data, sizes, cnt, W, H, C, sb, mb.ptr, stride, fb.ptr))
-        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download)
+        return rebuild_chain(self._buf, base, masks_packed, chunk_frames, chunk_bytes, rebuild, on_rebuilt, before_download, view)

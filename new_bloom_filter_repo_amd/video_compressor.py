@@ -451,6 +451,7 @@ class ImprovedVideoCompressor:
         self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
         self.last_pans, self.last_pan_offsets, self.last_scene_cuts = [], {}, []
         self.last_quality = self.last_digests = self.last_integrity = self.last_bad_frames = self.last_compressed_frames = self.last_timing = None
+        self.last_read = None
         self.profile_stages = False
         self.compressor = FixedVideoCompressor(verbose=verbose)
         self._bound_frames = {}                  # (frame shape, dtype) -> (the bound frame, its uniform value or None)
@@ -772,18 +773,14 @@ class ImprovedVideoCompressor:
     def _decode_key_rice(self, rec, lane=None, busy=None, digest_out=None, near=False):
         """A type-3 keyframe (near: a type-7 one) decoded on `lane` (default: lane 0): the frame, or a YUVFrame when the record says so.  digest_out: a list that
         receives the frame's digest, taken on the device where the frame was decoded, before its download."""
-        d = parse_near_key_record(rec) if near else parse_key_record(rec)
         if lane is None:
             lane = self._get_lanes(1)[0]
         t0 = time.perf_counter()
-        hook = None if digest_out is None else (lambda ptr, nbytes, cnt: digest_out.extend(int(x) for x in lane.digests(ptr, nbytes, cnt, nbytes)))
-        if near:
-            frame = lane.sample_coder().decode_near_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], d["bounds"], on_decoded=hook)
-        else:
-            frame = lane.sample_coder().decode_frame(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"], on_decoded=hook)
+        dev, yuv = self._decode_key_device(rec, lane, None, digest_out, near)
+        frame = lane.sample_coder().fetch(dev)
         if busy is not None:
             busy.append((t0, time.perf_counter()))
-        return YUVFrame(frame) if d["yuv"] else frame
+        return YUVFrame(frame) if yuv else frame
 
     def compress_video(self, frames, output_path=None, input_color_space="BGR"):
         """improved_video_compressor.py:358-450, same result dict.  Divergence: with inter-frames enabled
@@ -946,6 +943,122 @@ class ImprovedVideoCompressor:
             print(f"Decompressed {len(frames)} frames in {time.time() - start:.2f} seconds")
         return frames
 
+    def _decode_key_device(self, rec, lane, busy=None, digest_out=None, near=False):
+        """_decode_key_rice without the download: (the keyframe as an engine.DeviceFrame of `lane`, valid until the lane's sample coder
+        decodes its next frame; whether the record says YUV).  digest_out: as there."""
+        d = parse_near_key_record(rec) if near else parse_key_record(rec)
+        t0 = time.perf_counter()
+        hook = None if digest_out is None else (lambda ptr, nbytes, cnt: digest_out.extend(int(x) for x in lane.digests(ptr, nbytes, cnt, nbytes)))
+        dev = lane.sample_coder().decode_frame_device(d["stream"], d["height"], d["width"], d["channels"], d["itemsize"],
+                                                      d["bounds"] if near else None, on_decoded=hook)
+        if busy is not None:
+            busy.append((t0, time.perf_counter()))
+        return dev, bool(d["yuv"])
+
+    def read_frames(self, input_path=None, compressed_frames=None, start=0, stop=None, step=1, roi=None, scale=1, on_mismatch="raise"):
+        """Part of a container: the views of the frames range(start, stop, step), in order (stop=None: the end; a stop past the end is
+        clamped).  roi=(x, y, w, h), None = the whole frame; scale in {1, 2, 4, 8}: every s x s block of the region becomes its mean,
+        rounded half up (include/rbf.h, rbf_frame_view_batch, has the rule; view.view_host is its numpy twin).  A YUVFrame clip yields
+        YUVFrame views.  With roi=None, scale=1 and the full range the frames are decompress_video's, bit for bit.  ValueError for
+        step < 1, start < 0, an empty span, a bad region or a bad scale.
+        What is not needed is not decoded (container.read_span plans from the record types alone): type-1 keyframes outside the span
+        are not inflated, runs outside it take no lane, and a run stops at its last wanted frame.  What is not wanted is not
+        downloaded: inter-frames are viewed in the chain block they are rebuilt in, after the digests and the pan roll-back
+        (engine.rebuild_chain), type-3 / type-7 keyframes where they are decoded -- a keyframe a run hangs off goes into the chain block
+        device to device and never reaches the host.  A type-1 keyframe that is wanted itself is inflated on the host and viewed by the
+        numpy twin, as is everything on the frame-by-frame route (gop_batching=False).  The runs alternate over the lanes as in
+        decompress_video.
+        A container with a trailer is checked for every frame that is REBUILT (verify_digests, on_mismatch, IntegrityError and
+        last_bad_frames as in decompress_video, indices in clip numbering); the trailer's own digest and the pan table are checked whole.
+        self.last_read = {"records", "records_decoded", "frames_rebuilt", "frames_returned", "downloaded_bytes", "view_shape"}:
+        downloaded_bytes is the sum over the frame downloads the call made -- the view blocks of the chains and of the decoded
+        keyframes (masks and digests are not frames), counted where each download is made.  That holds on the batched route.  On the
+        frame-by-frame route (gop_batching=False) whole frames come back one call at a time and the figure is only a tally of the
+        type-3 / type-7 keyframes and type-4 frames that did (type-2 frames, rebuilt by scatter_values, are not in it)."""
+        from .view import View, check_region, view_host
+        if on_mismatch not in ("raise", "collect"):
+            raise ValueError("on_mismatch must be 'raise' or 'collect', got %r" % (on_mismatch,))
+        check_region(None, scale, 1, 1)                                      # (the scale; the region needs a frame's shape)
+        if roi is not None:
+            check_region(roi, scale, 1 << 62, 1 << 62)                       # (its form and signs, before anything is decoded)
+        t_all = time.perf_counter()
+        records, pan_table, stored = self._load_records(input_path, compressed_frames)
+        types = [ty for ty, _ in records]
+        keys, runs = container.read_span(types, start, stop, step)
+        wanted = list(range(int(start), len(types) if stop is None else min(int(stop), len(types)), int(step)))
+        log = _DigestLog(stored if self.verify_digests else None)
+        view = View(roi, scale)
+        self.last_timing = tm = {}
+        busy = []
+        fronts = {k for k, _, _, _ in runs}
+        key_pool = ThreadPoolExecutor(self.num_threads)
+
+        def key_job(rec):
+            frame = self.compressor.decompress_frame(rec)
+            return frame, frame_digest_host(frame_data(frame)) if log.checking else None
+        inflated = {j: key_pool.submit(key_job, records[j][1]) for j in sorted(fronts | set(keys)) if types[j] == KEY}
+        kviews, decoded = {}, {}                                             # wanted type-3 / type-7 keyframes -> their views; first record of a run -> its views
+
+        def wrap(a, yuv):
+            return YUVFrame(a) if yuv else a
+
+        def run_job(job, take):
+            k, lo, end, pos = job
+            base = inflated[k].result()[0] if types[k] == KEY else None      # (waits for the host's inflate without holding a lane)
+            with take() as lane:
+                yuv = isinstance(base, YUVFrame)
+                if base is None:
+                    base, yuv = self._decode_key_device(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
+                    if k in keys:
+                        kviews[k] = wrap(lane.sample_coder().fetch(base, view), yuv)
+                if lo is None:
+                    return None
+                return self._decode_run(base, [rec for _, rec in records[lo:end]], lane, key_pool, busy, types=types[lo:end],
+                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, end), view=view.at(pos), yuv=yuv)
+        try:
+            jobs = list(runs) + [(j, None, None, None) for j in keys if types[j] in (KEY_RICE, KEY_NEAR) and j not in fronts]     # lone type-3 keyframes: no run
+            if self.gop_batching and jobs:
+                for (_, lo, _, _), out in zip(jobs, self._on_lanes(jobs, run_job)):
+                    if lo is not None:
+                        decoded[lo] = out
+            else:
+                for k, lo, end, pos in jobs:                                 # frame by frame: whole frames on the host, the twin views them
+                    if types[k] == KEY:
+                        base = inflated[k].result()[0]
+                    else:
+                        base = self._decode_key_rice(records[k][1], digest_out=log.sink(k), near=types[k] == KEY_NEAR)
+                        view.downloads.append(base.nbytes)
+                        if k in keys:
+                            kviews[k] = wrap(view_host(frame_data(base), roi, scale), isinstance(base, YUVFrame))
+                    if lo is None:
+                        continue
+                    stabilised = []
+                    whole = self._decode_frame_by_frame(base, records[lo:end], _run_offsets(pan_table, lo, end), stabilised)
+                    log.host(lo, stabilised)                                 # (the digests describe the frames the records code)
+                    view.downloads.append(sum(f.nbytes for (ty, _), f in zip(records[lo:end], whole) if ty == INTER_RICE))
+                    decoded[lo] = [wrap(view_host(frame_data(whole[p]), roi, scale), isinstance(base, YUVFrame)) for p in pos]
+            for j, fut in inflated.items():
+                frame, digest = fut.result()
+                if log.checking:
+                    log.got[j] = (digest, "host")
+                if j in keys:
+                    kviews[j] = wrap(view_host(frame_data(frame), roi, scale), isinstance(frame, YUVFrame))
+            at = {lo + p: (lo, q) for _, lo, _, pos in runs for q, p in enumerate(pos)}
+            frames = [kviews[i] if i in kviews else decoded[at[i][0]][at[i][1]] for i in wanted]
+        finally:
+            key_pool.shutdown(wait=True)
+            self._release_lanes()
+        _close_timing(tm, t_all, busy)
+        tm["runs"], tm["lanes"] = len(runs), min(self.gpu_lanes, max(1, len(runs)))
+        rebuilt = container.span_records(keys, runs)
+        self.last_integrity, self.last_bad_frames = log.summary(rebuilt)
+        self.last_read = {"records": len(records), "records_decoded": rebuilt, "frames_rebuilt": rebuilt, "frames_returned": len(frames),
+                          "downloaded_bytes": int(sum(view.downloads)), "view_shape": tuple(frame_data(frames[0]).shape)}
+        if self.last_bad_frames and on_mismatch == "raise":
+            i = self.last_bad_frames[0]
+            raise IntegrityError(i, log.expected[i], log.got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEY_TYPES))
+        return frames
+
     def _decode_frame_by_frame(self, base, records, offsets=None, stabilised_out=None):
         """The frames of a run of inter-frame records after `base`, one record at a time (gop_batching=False).  offsets: the records'
         cumulative pan offsets (ox, oy), or None -- the records code the STABILISED frames, each is rolled back on the host (np.roll)
@@ -1006,7 +1119,7 @@ class ImprovedVideoCompressor:
                     raise ValueError("changed_values does not match the mask")
                 masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None, offsets=None):
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None, offsets=None, view=None, yuv=None):
         """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
         ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
         rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
@@ -1015,17 +1128,25 @@ class ImprovedVideoCompressor:
         the rebuild of a chunk and before its download (engine.rebuild_chain's hook).
         offsets: None, or the records' cumulative pan offsets (ox, oy): the records code the stabilised frames S(p) = F((p + c) mod (W, H)),
         so every rebuilt chunk is rolled back on the device (rbf_roll_frames with the negated offsets) after the digest hook and before
-        its download -- after its last frame, still stabilised, has been copied into the chain block's slot 0 for the next chunk."""
+        its download -- after its last frame, still stabilised, has been copied into the chain block's slot 0 for the next chunk.
+        view (view.View, read_frames): the run's frames stay on the device and the views of the records view.wanted (positions in recs)
+        come back instead, taken after the roll-back (engine.rebuild_chain has the hook order); base may then be an engine.DeviceFrame
+        of the lane -- a keyframe that was decoded there and never downloaded -- with yuv saying whether the clip's frames are
+        YUVFrames.  A viewed run is one stretch of one record type: a run that mixes types 2 and 4 (no compressor writes one) is a
+        ValueError here -- decompress_video reads it."""
         from . import _native as nat
-        from .engine import apply_chain
+        from .engine import DeviceFrame, apply_chain
         if lane is None:
             lane = self._get_lanes(1)[0]
         types = [INTER] * len(recs) if types is None else list(types)
         t0 = time.perf_counter()
-        base_arr = frame_data(base)
+        base_arr = base if isinstance(base, DeviceFrame) else frame_data(base)
+        yuv = isinstance(base, YUVFrame) if yuv is None else yuv
         H, W, ch, _ = frame_geometry(base_arr)
         n = H * W
         parsed = self._parse_run(base_arr, recs, types)
+        if view is not None and any(d["rice"] != parsed[0]["rice"] for d in parsed):
+            raise ValueError("a run that mixes record types 2 and 4 cannot be read in part: decompress_video reads it")
         inflate = lambda d: np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])[:d["value_count"]]
         own_pool = None
         if pool is None:
@@ -1070,18 +1191,18 @@ class ImprovedVideoCompressor:
             while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
                 j += 1
             if parsed[i]["rice"]:
-                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before)
+                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
             else:
-                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before)
+                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
             out += part
-            prev, i = part[-1], j
+            prev, i = part[-1] if view is None else None, j               # (a viewed run is one stretch: nothing continues it)
             if offsets is not None and i < len(parsed) and offsets[i - 1] != (0, 0):      # the next stretch continues the stabilised frame
                 prev = np.ascontiguousarray(np.roll(prev, (-offsets[i - 1][1], -offsets[i - 1][0]), axis=(0, 1)))
         t5 = time.perf_counter()
         self._tm_add(parse=t1 - t0, mask_decode=t2 - t1, inflate_wait=t3 - t2, check=t4 - t3, apply_chain=t5 - t4)
         if busy is not None:
             busy += [(t1, t2), (t4, t5)]
-        return [YUVFrame(f) for f in out] if isinstance(base, YUVFrame) else out
+        return [YUVFrame(f) for f in out] if yuv else out
 
     def verify_lossless(self, original_frames, decompressed_frames):
         return self.compressor.verify_lossless(original_frames, decompressed_frames)
