@@ -639,6 +639,35 @@ int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, co
                     uint32_t nframes, uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
                     const void *bounds_dev, uint32_t bound, rbf_error_row *rows_host);
 
+/* ---- hold sweep: what would every candidate bound do to every run of a block? ---------------------------------------------------- */
+/* Read-only, on a resident block in the layout of rbf_temporal_hold_runs, with runs as there: frame 0 and every frame f with
+ * run_starts[f] != 0 (HOST, nframes bytes, NULL: one run) start one.  candidates (HOST) are ncandidates = 1..8 strictly ascending
+ * bounds, each <= 255 (0 is legal as the first).  rows_host (HOST, runs * ncandidates rows; runs counted in frame order, a run of one
+ * frame included) receives in row r * ncandidates + i, for run r and Y = the block that rbf_temporal_hold_runs (lookahead == 0) or
+ * rbf_temporal_lookahead_runs (lookahead != 0) would leave with max_error = candidates[i] -- neither is run, nothing is written --
+ * over the run's frames, with the true unsigned difference of the hold:
+ *     sse      the sum of (X - Y)^2 over every sample, exact (the run's first frame contributes 0)
+ *     updates  the (pixel, frame) pairs with Y_t(p) != Y_{t-1}(p): the sum of the run's all-channel mask counts
+ *     max_abs  the largest |X - Y|
+ * A run of one frame has all fields 0; with candidate 0, Y = X: sse = 0 and updates is the exact mask count.  ONE read of the block
+ * serves every candidate: a lane owns a pixel of a run and walks the run's frames once with the state of four candidates in registers
+ * (more than four: two halves of a workgroup share a tile staged in LDS).  Under the look-ahead rule a segment's value is known only
+ * when it closes; the kernel keeps the segment's length n and, per sample, the first and second moments S1, S2 of d = x - (the segment's
+ * first sample), their min and max, and adds S2 - 2 w S1 + n w^2 on close (w = value - first sample).  Deterministic: per-wave partial
+ * sums go into scratch the context keeps and a second kernel folds them; no atomics.  BLOCKS until the rows are on the host.  A block
+ * whose base and stride are multiples of 16 goes through 16-byte loads in tiles of 256 pixels (128 with more than four candidates), any
+ * other sample-aligned layout and the pixels behind the last whole tile through a per-pixel kernel.  Not timed: there is no RBF_K_ id
+ * for it, as for rbf_cut_stats.  nframes == 0: RBF_OK, nothing is launched or written.
+ * RBF_EINVAL: channels outside 1..4, sample_bytes not 1 or 2, a null frames_dev, candidates or rows_host, a base or stride that is not
+ * a multiple of sample_bytes, a stride < width*height*channels*sample_bytes, ncandidates outside 1..8, candidates that do not strictly
+ * ascend.  RBF_ERANGE: a candidate > 255 (or >= 2^B); more than 128 runs; a run of more than 128 frames.  Everything is checked before
+ * anything is launched, and rows_host is untouched by a refused call. */
+typedef struct { uint64_t sse, updates; uint32_t max_abs, reserved; } rbf_sweep_row;
+int rbf_hold_sweep(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                   uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                   const uint8_t *run_starts, int lookahead,
+                   const uint32_t *candidates, uint32_t ncandidates, rbf_sweep_row *rows_host);
+
 /* ---- pan alignment: the global integer shift of a pair, and the roll that makes a block still ------------------------------------ */
 /* During a camera pan every pixel differs from the pixel at the same position one frame earlier; shifted by the pan it does not.  Let
  * F_f(p)[c] be sample c of pixel p = (x, y) of frame f, Y_f(p) = F_f(p)[0]; a pair is frame f against frame f-1; R is the range

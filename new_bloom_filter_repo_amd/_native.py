@@ -27,6 +27,8 @@ class FilterParams(ctypes.Structure):
 
 
 ERROR_ROW = np.dtype([("sse", "<u8"), ("differing", "<u8"), ("over_bound", "<u8"), ("max_abs", "<u4"), ("reserved", "<u4")])     # rbf_error_row
+SWEEP_ROW = np.dtype([("sse", "<u8"), ("updates", "<u8"), ("max_abs", "<u4"), ("reserved", "<u4")])     # rbf_sweep_row
+SWEEP_MAX_CANDIDATES = 8
 PAN_ROW = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("sad_zero", "<u8"), ("sad_best", "<u8"), ("moving_zero", "<u8"), ("moving_best", "<u8")])     # rbf_pan_stat
 PAN_MAX_RANGE = 32
 
@@ -110,6 +112,7 @@ _PROTOS = {
     "rbf_rice_decode_intra_near": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, ctypes.POINTER(_u32), _vp]),
     "rbf_cut_stats": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "rbf_error_stats": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "rbf_hold_sweep": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _int, ctypes.POINTER(_u32), _u32, _vp]),
     "rbf_pan_search": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "rbf_roll_frames": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _i32p]),
     "rbf_frame_view_batch": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u32), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64]),

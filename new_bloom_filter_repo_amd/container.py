@@ -159,6 +159,34 @@ def stat_tolerance(max_error, bounds_min, hold_mode, sample_bytes):
     return min(tol if hold_mode == "first" else 2 * tol, (1 << (8 * sample_bytes)) - 1)
 
 
+def sweep_candidates(cap):
+    """The bounds a target_psnr call tries for every run (GopCoder.hold_sweep takes at most eight): 1..cap when cap <= 8, else the
+    distinct values of round(cap * i / 8), i = 1..8 -- ascending, the last one is cap.  cap: max_error, 1..255."""
+    cap = int(cap)
+    if not 1 <= cap <= 255:
+        raise ValueError("the sweep's ceiling must be in 1..255, got %r" % (cap,))
+    if cap <= 8:
+        return list(range(1, cap + 1))
+    return sorted({int(round(cap * i / 8)) for i in range(1, 9)})
+
+
+def sse_budget(target_psnr, bits, samples):
+    """The largest sum of squared errors `samples` samples of `bits` bits may carry at a PSNR of at least target_psnr dB (peak
+    2^bits - 1): floor(samples * peak^2 / 10^(target_psnr / 10)).  The one place that forms it."""
+    peak = (1 << int(bits)) - 1
+    tenths = float(target_psnr) / 10.0
+    return 0 if tenths > 300.0 else int(int(samples) * peak * peak / 10.0 ** tenths)     # (10^300: no clip's sse reaches it)
+
+
+def choose_bound(rows, candidates, budget):
+    """The bound of one run under a target: the LARGEST candidate whose sse (rows: the run's GopCoder.hold_sweep rows, one per
+    candidate) is within `budget` -- whether or not sse grows with the bound -- and 0, the exact run, when none is."""
+    for row, d in reversed(list(zip(rows, candidates))):
+        if int(row["sse"]) <= budget:
+            return int(d)
+    return 0
+
+
 def rebase_cuts(offsets, cuts, starts, W, H):
     """A scene cut is a keyframe, coded from the caller's array, so its run starts at offset 0 like every other: (new offsets, rel) for
     a block whose frames were rolled by `offsets` (pan_offsets) and in which the frames `cuts` then became run starts (starts: all the

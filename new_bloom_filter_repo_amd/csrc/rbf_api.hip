@@ -20,6 +20,7 @@
 #include "rbf_kernels_digest.h"
 #include "rbf_kernels_cut.h"
 #include "rbf_kernels_error.h"
+#include "rbf_kernels_sweep.h"
 #include "rbf_kernels_pan.h"
 #include "rbf_kernels_view.h"
 #include "rbf_rice_host.h"
@@ -1815,6 +1816,92 @@ int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, co
     hipLaunchKernelGGL(k_error_reduce, dim3(nframes), dim3(WG_THREADS), 0, ctx->stream, partials, rows, (ErrorRow *)ctx->err_rows.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rows_host, ctx->err_rows.p, (size_t)nframes * sizeof(ErrorRow), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RBF_OK;
+}
+
+// ---- hold sweep: what every candidate bound would do to every run of a block (rbf_kernels_sweep.h); read-only on the block, blocks
+// until the rows are on the host
+int rbf_hold_sweep(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_bytes, uint32_t nframes,
+                   uint32_t width, uint32_t height, uint32_t channels, uint32_t sample_bytes,
+                   const uint8_t *run_starts, int lookahead,
+                   const uint32_t *candidates, uint32_t ncandidates, rbf_sweep_row *rows_host)
+{
+    static_assert(sizeof(SweepRow) == sizeof(rbf_sweep_row) && sizeof(rbf_sweep_row) == 24, "the kernels write the ABI's rows");
+    static_assert(SWEEP_MAX_RUN * 4 * 255 * 255 <= 0xFFFFFFFFu / 64, "a wave's sse of a run fits 32 bits");
+    if (int r = set_device(ctx)) return r;
+    const uint32_t pixel = channels * sample_bytes;
+    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
+    LayoutRules rules;
+    rules.samples = channels; rules.channels = true;
+    if (int r = check_layout(l, nframes, rules)) return r;
+    if (ncandidates < 1 || ncandidates > SWEEP_MAX_CANDIDATES) return fail(RBF_EINVAL, "ncandidates must be 1..%u, got %u", SWEEP_MAX_CANDIDATES, ncandidates);
+    if (!candidates) return fail(RBF_EINVAL, "null candidates");
+    uint64_t cands = 0;
+    for (uint32_t i = 0; i < ncandidates; ++i) {
+        if (i && candidates[i] <= candidates[i - 1])
+            return fail(RBF_EINVAL, "candidates must strictly ascend: candidates[%u] = %u after %u", i, candidates[i], candidates[i - 1]);
+        if (candidates[i] > 255) return fail(RBF_ERANGE, "candidate %u above 255", candidates[i]);
+        cands |= (uint64_t)candidates[i] << (8 * i);
+    }
+    if (nframes == 0) return RBF_OK;
+    if (!frames_dev || !rows_host) return fail(RBF_EINVAL, "null pointer");
+    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    if (frame_stride_bytes < frame_bytes)
+        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    // the runs: frame 0 and every marked frame start one; a run of one frame keeps its rows (of zeros)
+    HoldRuns runs{};
+    uint32_t count = 0;
+    for (uint32_t a = 0; a < nframes;) {
+        uint32_t b = a + 1;
+        while (b < nframes && !(run_starts && run_starts[b])) ++b;
+        if (count == HOLD_MAX_RUNS) return fail(RBF_ERANGE, "more than %u runs", HOLD_MAX_RUNS);
+        if (b - a > SWEEP_MAX_RUN) return fail(RBF_ERANGE, "run of %u frames at frame %u: at most %u", b - a, a, SWEEP_MAX_RUN);
+        runs.first[count] = a; runs.len[count] = b - a;
+        ++count;
+        a = b;
+    }
+    // workgroup tiles through 16-byte loads where the layout allows them, the per-pixel kernel for everything else; more than four
+    // candidates: two halves of a workgroup share a tile of half the size
+    const uint32_t groups = ncandidates > SWEEP_GROUP ? 2 : 1, tile = WG_THREADS / groups;
+    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
+    const uint64_t tiles = vec ? n / tile : 0, first_px = tiles * tile;
+    const uint64_t bx_px = (n - first_px + tile - 1) / tile;
+    if (tiles > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    const uint64_t rows = (tiles + bx_px) * (tile / WAVE);        // a row per wave, run and candidate; every row is written by every call
+    const uint32_t cells = count * ncandidates;
+    if (int r = ctx->sweep_partials.reserve((size_t)cells * rows * SWEEP_WORDS * 4)) return r;
+    if (int r = ctx->sweep_rows.reserve((size_t)cells * sizeof(SweepRow))) return r;
+    const uint8_t *const frames = (const uint8_t *)frames_dev;
+    uint32_t *const partials = ctx->sweep_partials.p;
+    if (tiles) {
+        const dim3 grid((uint32_t)tiles, count), block(WG_THREADS);
+#define RBF_SWEEP(S, C)                                                                                                                          \
+    do {                                                                                                                                         \
+        if (lookahead)                                                                                                                           \
+            hipLaunchKernelGGL((k_hold_sweep<S, C, true>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, groups, cands, ncandidates, partials, rows, runs); \
+        else                                                                                                                                     \
+            hipLaunchKernelGGL((k_hold_sweep<S, C, false>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, groups, cands, ncandidates, partials, rows, runs); \
+    } while (0)
+        if (sample_bytes == 1) { if (channels == 1) RBF_SWEEP(uint8_t, 1); else if (channels == 2) RBF_SWEEP(uint8_t, 2); else if (channels == 3) RBF_SWEEP(uint8_t, 3); else RBF_SWEEP(uint8_t, 4); }
+        else { if (channels == 1) RBF_SWEEP(uint16_t, 1); else if (channels == 2) RBF_SWEEP(uint16_t, 2); else if (channels == 3) RBF_SWEEP(uint16_t, 3); else RBF_SWEEP(uint16_t, 4); }
+#undef RBF_SWEEP
+    }
+    if (first_px < n)
+        by_sample_width(sample_bytes, [&](auto s) {
+            using S = decltype(s);
+            const dim3 grid((uint32_t)bx_px, count), block(WG_THREADS);
+            if (lookahead)
+                hipLaunchKernelGGL((k_hold_sweep_px<S, true>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, groups,
+                                   cands, ncandidates, partials, rows, tiles * (tile / WAVE), runs);
+            else
+                hipLaunchKernelGGL((k_hold_sweep_px<S, false>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, groups,
+                                   cands, ncandidates, partials, rows, tiles * (tile / WAVE), runs);
+        });
+    hipLaunchKernelGGL(k_sweep_reduce, dim3(cells), dim3(WG_THREADS), 0, ctx->stream, partials, rows, (SweepRow *)ctx->sweep_rows.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rows_host, ctx->sweep_rows.p, (size_t)cells * sizeof(SweepRow), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RBF_OK;
 }

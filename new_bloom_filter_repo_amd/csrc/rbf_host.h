@@ -116,6 +116,8 @@ struct rbf_ctx {
     DevBuf<uint32_t> cut_partials;   // scene-cut statistics (rbf_kernels_cut.h): three sums per wave and pair of the call
     DevBuf<uint32_t> err_partials;   // quality report (rbf_kernels_error.h): six words per wave and frame of the call
     DevBuf<void> err_rows;           // ... and the folded rows (rbf_error_row), a frame each, on their way to the host
+    DevBuf<uint32_t> sweep_partials; // hold sweep (rbf_kernels_sweep.h): four words per wave, run and candidate of the call
+    DevBuf<void> sweep_rows;         // ... and the folded rows (rbf_sweep_row), a (run, candidate) each, on their way to the host
     DevBuf<uint32_t> pan_partials;   // pan search (rbf_kernels_pan.h): (2R+1)^2 sums per tile and pair of the call
     DevBuf<uint32_t> pan_moving;     // ... two counts per wave and pair
     DevBuf<void> pan_rows;           // ... the folded rows (rbf_pan_stat), a pair each: the pick's shift stays here for the moving kernel

@@ -193,6 +193,7 @@ class GopCoder:
         """Name the keyframes inside the block for the following encode() calls (see the constructor): a coder is sized by its frame
         count, not by where its runs start, so one coder serves every block of a stream whatever the keyframe interval."""
         self.run_starts = None
+        self.run_bounds = None                        # (bounds are per run: new runs, no bounds)
         self.skipped = [False] * self.pairs
         if run_starts:
             self.run_starts = (ctypes.c_uint8 * self.F)()
@@ -202,6 +203,63 @@ class GopCoder:
                 if int(t) > 0:
                     self.run_starts[int(t)] = 1
                     self.skipped[int(t) - 1] = True
+
+    def runs(self):
+        """[(first frame, end)] of the block's runs in frame order, a run of one frame included: frame 0 and every run start open one."""
+        starts = [0] + [t for t in range(1, self.F) if self.run_starts is not None and self.run_starts[t]]
+        return list(zip(starts, starts[1:] + [self.F]))
+
+    def set_run_bounds(self, bounds):
+        """A bound PER RUN in place of the one max_error, for the following encode() calls: one integer in 0..max_error per run of runs()
+        (the coder's max_error is the ceiling: it is what the coder was checked against and what error_stats() counts over_bound with),
+        or None to return to the single max_error.  encode_begin() then calls the scalar hold entry (hold_mode's) once per maximal
+        stretch of consecutive runs that share a bound -- with the stretch's first frame, its frame count and its own slice of the run
+        starts -- and not at all for a stretch whose bound is 0: those runs are coded exactly.  The records carry no bound, so every
+        decoder reads the result.  set_run_starts() forgets the bounds: call it first.  Not with error_bounds."""
+        if bounds is None:
+            self.run_bounds = None
+            return
+        if self.bounds is not None or not self.max_error:
+            raise ValueError("run bounds replace a scalar max_error > 0 (their ceiling): not with error_bounds, not on a lossless coder")
+        bounds = list(bounds)
+        if len(bounds) != len(self.runs()):
+            raise ValueError("one bound per run: the block has %d runs, got %d bounds" % (len(self.runs()), len(bounds)))
+        for d in bounds:
+            if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= d <= self.max_error:
+                raise ValueError("a run's bound must be an integer in 0..max_error = %d, got %r" % (self.max_error, d))
+        self.run_bounds = [int(d) for d in bounds]
+
+    def _hold_stretches(self):
+        """[(first frame, end, bound)] of the maximal stretches of consecutive runs that share a non-zero bound (set_run_bounds)."""
+        runs, out, i = self.runs(), [], 0
+        while i < len(runs):
+            j = i
+            while j + 1 < len(runs) and self.run_bounds[j + 1] == self.run_bounds[i]:
+                j += 1
+            if self.run_bounds[i]:
+                out.append((runs[i][0], runs[j][1], self.run_bounds[i]))
+            i = j + 1
+        return out
+
+    def hold_sweep(self, candidates, lookahead=None, gop=0):
+        """What every candidate bound would do to every run of resident GOP `gop` (rbf_hold_sweep, include/rbf.h): a structured array
+        (_native.SWEEP_ROW) of shape (runs, candidates) -- row [r, i]: sse, updates and max_abs of run r of runs() under the hold with
+        max_error = candidates[i], first-value or (lookahead) look-ahead; default: the coder's hold_mode.  candidates: 1..8 strictly
+        ascending integers <= 255, 0 allowed as the first.  Read-only, ONE read of the block AS IT IS NOW with the coder's current run
+        starts, whatever the number of candidates: call it before any hold has rewritten the block, the caveat of cut_stats().  Blocks
+        until the rows are on the host."""
+        if self.planar_luma or self.frames is None:
+            raise ValueError("the hold sweep reads the interleaved frames: not with planar_luma")
+        assert 0 <= gop < self.resident_gops
+        cands = [int(d) for d in candidates]
+        if any(d < 0 for d in cands):
+            raise ValueError("candidates must be non-negative, got %r" % (cands,))
+        look = self.hold_mode == "lookahead" if lookahead is None else bool(lookahead)
+        rows = np.zeros((len(self.runs()), len(cands)), dtype=nat.SWEEP_ROW)
+        nat.check(nat.lib().rbf_hold_sweep(self.ctx.handle, self._block_ptr(self.frames, gop), self.frame_bytes, self.F, self.W, self.H,
+                                           self.C, self.sb, self.run_starts, int(look), (ctypes.c_uint32 * max(1, len(cands)))(*cands),
+                                           len(cands), rows.ctypes.data))
+        return rows
 
     @staticmethod
     def strides(n):
@@ -347,7 +405,18 @@ class GopCoder:
         else:
             src, fstride, pitch, pstride = self.frames.ptr + gop * self.frame_bytes * self.F, self.frame_bytes, self.W * self.C * self.sb, self.C * self.sb
         geometry = (self.ctx.handle, src, fstride, self.F, self.W, self.H, self.C, self.sb)
-        if (self.max_error or self.bounds is not None) and self.hold_mode == "lookahead":
+        if self.run_bounds is not None:               # a bound per run: the scalar entry, once per stretch of runs that share a bound
+            if len(self.run_bounds) != len(self.runs()):
+                raise ValueError("the run bounds no longer fit the block's runs: set_run_bounds() after set_run_starts()")
+            look = self.hold_mode == "lookahead"
+            if not look or gop not in self._held:
+                hold = nat.lib().rbf_temporal_lookahead_runs if look else nat.lib().rbf_temporal_hold_runs
+                for a, b, d in self._hold_stretches():
+                    marks = None if self.run_starts is None else (ctypes.c_uint8 * (b - a))(*self.run_starts[a:b])
+                    nat.check(hold(self.ctx.handle, src + a * fstride, fstride, b - a, self.W, self.H, self.C, self.sb, d, marks))
+                if look:
+                    self._held.add(gop)
+        elif (self.max_error or self.bounds is not None) and self.hold_mode == "lookahead":
             if gop not in self._held:                 # not idempotent: once per load_frames(); after that the block IS its held sequence
                 if self.bounds is not None:
                     nat.check(nat.lib().rbf_temporal_lookahead_runs_map(*geometry, self.bounds.ptr, self.run_starts))

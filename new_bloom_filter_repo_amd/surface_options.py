@@ -23,7 +23,7 @@ _REFUSALS = {"gop_batching": lambda f, name: "%s needs gop_batching=True: the fr
              "all_channels": lambda f, name: "%s %s every sample of a pixel: it needs mask_channels='all'" % (name, f.verb)}
 
 Options = namedtuple("Options", "pan_range error_bounds quality_report scene_cuts max_error hold_mode frame_digests verify_digests near "
-                                "sample_codec mask_channels inter_frames keyframe_interval gop_batching block_frames gpu_lanes bounded_keyframes")
+                                "sample_codec mask_channels inter_frames keyframe_interval gop_batching block_frames gpu_lanes bounded_keyframes target_psnr")
 
 
 def _is_int(v):
@@ -39,7 +39,7 @@ def _require(feature, name, have):
 
 def check_options(keyframe_interval=30, inter_frames=None, gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma",
                   sample_codec="zlib", max_error=0, frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False,
-                  error_bounds=None, quality_report=False, pan_range=0, bounded_keyframes=False):
+                  error_bounds=None, quality_report=False, pan_range=0, target_psnr=None, bounded_keyframes=False):
     """The checked and normalised keywords of ImprovedVideoCompressor as an Options tuple, or the ValueError of the first refusal.
     `near` is the name the near-lossless stage goes by in messages ("error_bounds", "max_error > 0") or None.  The default block is
     two keyframe intervals (a multiple of the interval: every block of a stream has the same shape), at most 128 frames: small blocks
@@ -89,11 +89,27 @@ def check_options(keyframe_interval=30, inter_frames=None, gop_batching=True, bl
                              "not with error_bounds of shape %r" % (e.shape,))
         if e is not None and not e.any():
             raise ValueError("bounded_keyframes=True needs a bound: error_bounds is all zero")
+    if target_psnr is not None:
+        if isinstance(target_psnr, bool) or not isinstance(target_psnr, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(target_psnr) or not target_psnr > 0:
+            raise ValueError("target_psnr must be a finite positive number of dB, got %r" % (target_psnr,))
+        if error_bounds is not None:
+            raise ValueError("target_psnr picks one scalar bound per run (the sweep is scalar): not with error_bounds")
+        if not max_error:
+            raise ValueError("target_psnr picks every run's bound from 1..max_error: it needs max_error > 0 as the ceiling")
+        if max_error > 255:
+            raise ValueError("target_psnr sweeps bounds of at most 255: max_error=%d is above that" % max_error)
+        if bounded_keyframes:
+            raise ValueError("target_psnr measures the holds against exact keyframes (a keyframe would be quantised before the sweep "
+                             "could see what the hold hangs off): not with bounded_keyframes=True")
+        target_psnr = float(target_psnr)
     I = max(1, int(keyframe_interval))
     block_frames = max(2, int(block_frames)) if block_frames else min(128, max(2, 2 * I if 2 * I <= 128 else I))
+    if target_psnr is not None and block_frames > 128:
+        raise ValueError("target_psnr sweeps blocks of at most 128 runs of at most 128 frames: not with block_frames=%d" % block_frames)
     return Options(pan_range, error_bounds, bool(quality_report), bool(scene_cuts), max_error, hold_mode, bool(frame_digests),
                    bool(verify_digests), near, sample_codec, mask_channels, inter_frames, I, bool(gop_batching), block_frames,
-                   max(1, int(gpu_lanes)), bool(bounded_keyframes))
+                   max(1, int(gpu_lanes)), bool(bounded_keyframes), target_psnr)
 
 
 def check_blocks(options, blocks, first_index, I):

@@ -196,3 +196,19 @@ def make_camera_gop(seed, width, height, nframes, moving=0.01, dtype=np.uint8, c
             flip.reshape(-1)[rng.integers(0, n, 3)] ^= True
         emit(cur)
     return frames
+
+
+def add_run_noise(frames, interval, amplitudes, seed=0):
+    """Sensor noise whose amplitude varies from run to run: a copy of `frames` (an (F, H, W, C) array or a list of frames, uint8 / uint16)
+    in which every sample of run r -- frames r * interval .. (r + 1) * interval - 1 -- carries independent uniform integer noise in
+    [-a, a], a = amplitudes[r % len(amplitudes)], clipped to the sample range.  A clean stretch tolerates a large near-lossless bound
+    at a given PSNR, a noisy one a small bound: what ImprovedVideoCompressor(target_psnr=...) tells apart.  Returns an array."""
+    x = np.stack([np.asarray(f) for f in frames]) if not isinstance(frames, np.ndarray) else frames
+    dtype, top = x.dtype, int(np.iinfo(x.dtype).max)
+    rng = np.random.default_rng(seed)
+    out = x.copy()
+    for r, lo in enumerate(range(0, len(x), interval)):
+        a = int(amplitudes[r % len(amplitudes)])
+        run = x[lo:lo + interval].astype(np.int32)
+        out[lo:lo + interval] = np.clip(run + rng.integers(-a, a + 1, run.shape), 0, top).astype(dtype)
+    return out

@@ -153,7 +153,7 @@ _CoderSpec = namedtuple("_CoderSpec", "width height nframes channels sample_byte
 class _BlockRecords:
     """What _encode_block returns for a block the GPU coded."""
 
-    def __init__(self, pairs=(), digests=None, cuts=(), pan_offsets=None, pans=(), quality=None, near_keys=None):
+    def __init__(self, pairs=(), digests=None, cuts=(), pan_offsets=None, pans=(), quality=None, near_keys=None, run_bounds=()):
         self.pairs = list(pairs)                 # per pair: the future of its inter-frame record, or None (needs a keyframe, or is one)
         self.digests = digests                   # frame_digests=True: uint64 per frame of the block, or None
         self.cuts = tuple(cuts)                  # scene_cuts=True: the block indices the cut rule made run starts
@@ -161,6 +161,7 @@ class _BlockRecords:
         self.pans = pans                         # ... and [(block index, dx, dy)] of the pairs that adopted a shift
         self.quality = quality                   # quality_report=True: GopCoder.error_stats() of the block, a row per frame
         self.near_keys = near_keys or {}         # bounded_keyframes=True: block index of a run first -> its type-7 record
+        self.run_bounds = list(run_bounds)       # target_psnr: (block index of a run's first frame, its bound, sse, updates) per run
 
 
 def _union_seconds(intervals):
@@ -231,7 +232,7 @@ class _RangeRecords:
         self.comp, self.frames, self.first_index, self.start, self.stop, self.pool = comp, frames, first_index, start, stop, pool
         self.inter_type = INTER_RICE if comp.sample_codec == "rice" else INTER
         self.records, self.pending, self.digests, self.quality, self.pan_table = {}, {}, {}, {}, {}
-        self.gpu_keys, self.scene_cuts, self.pans = set(), [], []
+        self.gpu_keys, self.scene_cuts, self.pans, self.run_bounds = set(), [], [], []
 
     def key(self, t):
         """Frame t is a keyframe: on a lane later (a type-3 record can carry it) or in zlib-9 on the host threads from now on."""
@@ -280,6 +281,7 @@ class _RangeRecords:
         cut = set(got.cuts)                      # a cut frame is a run start of its block like a rule keyframe
         self.scene_cuts += [lo + j for j in sorted(cut) if start <= lo + j < stop]
         self.pans += [(lo + j, dx, dy) for j, dx, dy in got.pans if start <= lo + j < stop]
+        self.run_bounds += [(lo + j, d, sse, updates) for j, d, sse, updates in got.run_bounds if start <= lo + j < stop]
         self.near_key(lo, got, 0)
         self.digest_of(lo, got.digests, 0)
         for j in range(1, len(seg)):
@@ -323,6 +325,7 @@ class _RangeRecords:
         tm["zlib_wait"] = time.perf_counter() - t_wait                       # what the host threads' zlib-9 still owed after the last block left the GPU
         comp.last_digests = [d if isinstance(d, int) else int(d.result()) for d in (self.digests[u] for u in range(start, stop))] if comp.frame_digests else None
         comp.last_scene_cuts, comp.last_pans, comp.last_pan_offsets = sorted(self.scene_cuts), sorted(self.pans), self.pan_table
+        comp.last_run_bounds = sorted(self.run_bounds)
         comp.last_quality = comp._quality_dicts(frames, first_index, start, stop, self.quality) if comp.quality_report else None
         return [self.records[u] for u in range(start, stop)]
 
@@ -333,8 +336,8 @@ class ImprovedVideoCompressor:
                  num_threads=None, use_direct_yuv=False, verbose=False, ctx=None, inter_frames=None,
                  gop_batching=True, block_frames=None, gpu_lanes=2, mask_channels="luma", sample_codec="zlib", max_error=0,
                  frame_digests=False, verify_digests=True, hold_mode="first", scene_cuts=False, error_bounds=None, quality_report=False,
-                 pan_range=0, bounded_keyframes=False):
-        """Reference signature (improved_video_compressor.py:318-327) plus sixteen keyword-only extras:
+                 pan_range=0, target_psnr=None, bounded_keyframes=False):
+        """Reference signature (improved_video_compressor.py:318-327) plus seventeen keyword-only extras:
         ctx (library context), gop_batching (False: one set of C-ABI calls per inter-frame instead of one
         per block; both write the same bytes), block_frames (consecutive frames handed to the GPU in ONE
         rbf_encode_runs launch sequence -- several GOPs, cut at the keyframes; default 2 GOPs, at most 128
@@ -415,6 +418,24 @@ class ImprovedVideoCompressor:
         max_error > 0 does); not with error_bounds that differ from pixel to pixel (the bound map would no longer sit on the pixels it
         was drawn for; per-channel bounds are fine).  A block whose frames are not larger than 2R in both directions is coded as
         without the keyword.  last_pans lists (global frame index, dx, dy) for every pair of the last encode_range that adopted a shift.
+        target_psnr: None (default) -- the bound is max_error, for every run; nothing is launched and the container is today's, byte for
+        byte.  T, a finite positive number of dB -- the caller names the quality to keep instead of the bound, and max_error = cap >= 1
+        becomes the bound's CEILING.  After a block's upload, pan alignment and cut detection -- the runs are final, the block is still
+        -- ONE pass over the block (GopCoder.hold_sweep: rbf_hold_sweep) measures what each candidate bound
+        (container.sweep_candidates: 1..cap, or eight values up to a cap above 8) would do to each run under hold_mode's rule, and every
+        run gets the largest candidate whose sum of squared errors fits its budget (container.choose_bound; container.sse_budget:
+        floor(N (2^B - 1)^2 / 10^(T / 10)), N the samples of all the run's frames), or 0 -- exact -- when none does.  The hold then
+        runs with a bound per run (GopCoder.set_run_bounds) and everything behind it is the code it is: a clean run takes the cap while
+        a noisy one stays tight.  So every run's PSNR over all samples of all its frames is >= T, every sample is within cap of the
+        original, keyframes are exact, and -- the records carry no bound -- a fresh default compressor decodes the container.  A T
+        that every run meets at the cap writes the bytes of max_error=cap; a T no candidate meets writes the lossless
+        mask_channels="all" container.  A block the GPU cannot batch is coded exactly, as with max_error.  Needs max_error in 1..255,
+        block_frames <= 128 (the sweep takes 128 runs of up to 128 frames) and everything max_error > 0 needs; not with error_bounds (the sweep is scalar) and not with bounded_keyframes (the
+        keyframe would be quantised before the sweep could see what the hold hangs off).  Combines with scene_cuts, pan_range,
+        frame_digests, quality_report, hold_mode and sample_codec as max_error does.  The cut statistic keeps the CAP's tolerance: a
+        run that ends up with a smaller bound moves more than the statistic assumed and may miss a cut -- that costs bytes, never
+        correctness.  last_run_bounds lists (global index of the run's first frame, its bound, sse, updates) for every run of the
+        last encode_range; compress_video's result carries it as "run_bounds" next to "target_psnr".
         bounded_keyframes: False (default) -- keyframes are exact, nothing is launched and the container is today's, byte for byte.
         True -- every keyframe that is a run first of a batched block (rule keyframes and scene cuts alike) is coded within the bound
         instead of exactly: a closed-loop quantiser inside the keyframe predictor (GopCoder.quantise_run_starts:
@@ -437,8 +458,8 @@ class ImprovedVideoCompressor:
         leg; profile_stages=True synchronises between the stages of a block so that it can tell them apart)."""
         o = self._options = check_options(keyframe_interval, inter_frames, gop_batching, block_frames, gpu_lanes, mask_channels, sample_codec,
                                           max_error, frame_digests, verify_digests, hold_mode, scene_cuts, error_bounds, quality_report, pan_range,
-                                          bounded_keyframes)
-        self.bounded_keyframes = o.bounded_keyframes
+                                          target_psnr, bounded_keyframes)
+        self.bounded_keyframes, self.target_psnr = o.bounded_keyframes, o.target_psnr
         self.pan_range, self.error_bounds, self.quality_report, self.scene_cuts = o.pan_range, o.error_bounds, o.quality_report, o.scene_cuts
         self.max_error, self.hold_mode, self._near = o.max_error, o.hold_mode, o.near
         self.frame_digests, self.verify_digests = o.frame_digests, o.verify_digests
@@ -449,7 +470,7 @@ class ImprovedVideoCompressor:
         self.num_threads = max(1, num_threads or min(64, os.cpu_count() or 1))     # zlib of keyframes / changed values
         self.use_direct_yuv, self.verbose = use_direct_yuv, verbose
         self.chain_chunk_frames = 64             # frames per device-side rebuild chunk of a run (engine.rebuild_chain)
-        self.last_pans, self.last_pan_offsets, self.last_scene_cuts = [], {}, []
+        self.last_pans, self.last_pan_offsets, self.last_scene_cuts, self.last_run_bounds = [], {}, [], []
         self.last_quality = self.last_digests = self.last_integrity = self.last_bad_frames = self.last_compressed_frames = self.last_timing = None
         self.last_read = None
         self.profile_stages = False
@@ -568,9 +589,10 @@ class ImprovedVideoCompressor:
         """Upload `block` into the coder and make it what the hold and the mask stage are to see: aligned (pan_range: GopCoder.align_pans),
         looked at for cuts (scene_cuts: GopCoder.cut_stats, container.cut_frames -- the cuts join the run starts) and, where a cut carries
         an offset, re-based (container.rebase_cuts).  tol: container.stat_tolerance -- the block is looked at before any hold rewrites
-        it, and a pixel the hold will keep still is not moving.  Returns (run starts, offsets, adopted, cuts, times): the frames'
-        cumulative offsets (ox, oy) or None, the pairs [(j, dx, dy)] that adopted a shift, the cut frames, and when the upload and the
-        alignment were done (time.perf_counter)."""
+        it, and a pixel the hold will keep still is not moving.  With target_psnr the runs, final by then, get their bounds
+        (_choose_run_bounds) last of all.  Returns (run starts, offsets, adopted, cuts, times, run bounds): the frames' cumulative
+        offsets (ox, oy) or None, the pairs [(j, dx, dy)] that adopted a shift, the cut frames, when the upload, the alignment and the
+        cut statistic were done (time.perf_counter), and [(first frame, bound, sse, updates)] per run, [] without a target."""
         coder.load_frames(block)                 # (synchronous: the frames are pageable host memory)
         t_up = time.perf_counter()
         starts, offsets, adopted, cuts = list(run_starts), None, [], []
@@ -586,7 +608,28 @@ class ImprovedVideoCompressor:
                     offsets, rel = container.rebase_cuts(offsets, cuts, starts, coder.W, coder.H)
                     coder.roll_frames(rel)
                 adopted = [row for row in adopted if row[0] not in cuts]      # (the pair in front of a cut is not coded)
-        return starts, offsets, adopted, cuts, (t_up, t_pan)
+        t_cut = time.perf_counter()
+        run_bounds = self._choose_run_bounds(coder) if self.target_psnr is not None else []
+        return starts, offsets, adopted, cuts, (t_up, t_pan, t_cut), run_bounds
+
+    def _choose_run_bounds(self, coder):
+        """target_psnr: sweep the resident block, still and with its final runs (GopCoder.hold_sweep: every candidate of
+        container.sweep_candidates(max_error) for every run in ONE read of the block), give every run the largest candidate whose sse
+        fits the run's budget (container.choose_bound, container.sse_budget over all samples of all the run's frames) and hand the
+        bounds to the coder (set_run_bounds).  Returns [(first frame of the run in the block, bound, sse, updates)]; a run that stays
+        exact reports sse 0 and its exact update count (one more sweep, candidate 0, only when there is such a run)."""
+        candidates = container.sweep_candidates(self.max_error)
+        rows, runs = coder.hold_sweep(candidates), coder.runs()
+        per_frame = coder.W * coder.H * coder.C
+        bounds = [container.choose_bound(rows[r], candidates, container.sse_budget(self.target_psnr, 8 * coder.sb, (b - a) * per_frame))
+                  for r, (a, b) in enumerate(runs)]
+        exact = coder.hold_sweep([0]) if not all(bounds) else None
+        coder.set_run_bounds(bounds)
+        out = []
+        for r, ((a, _), d) in enumerate(zip(runs, bounds)):
+            row = rows[r][candidates.index(d)] if d else exact[r][0]
+            out.append((a, d, int(row["sse"]), int(row["updates"])))
+        return out
 
     @staticmethod
     def _pair_jobs(res, values, fallback, pool, n, C, itemsize, rice):
@@ -644,7 +687,7 @@ class ImprovedVideoCompressor:
         block = _as_block([frame_data(f) for f in seg])
         tol = container.stat_tolerance(spec.max_error, None if spec.error_bounds is None else spec.error_bounds.min(), spec.hold_mode, sb)
         t1 = time.perf_counter()
-        _, offsets, adopted, cuts, (t_up, t_pan) = self._prepare_block(coder, block, run_starts, tol)
+        _, offsets, adopted, cuts, (t_up, t_pan, t_cut), run_bounds = self._prepare_block(coder, block, run_starts, tol)
         t_q = time.perf_counter()
         near_keys = {}
         if self.bounded_keyframes:               # the run firsts become their quantised selves before the hold looks at them
@@ -673,14 +716,16 @@ class ImprovedVideoCompressor:
         t5 = time.perf_counter()
         self._tm_add(stack=t1 - t0, upload=t_up - t1, gpu_encode=t3 - t2, download_rows=t4 - t3, value_gather=t5 - t4)
         if self.scene_cuts:
-            self._tm_add(cut_stats=t_q - t_pan)   # (one launch sequence, a wait and 24 bytes per pair)
+            self._tm_add(cut_stats=t_cut - t_pan)   # (one launch sequence, a wait and 24 bytes per pair)
+        if self.target_psnr is not None:
+            self._tm_add(hold_sweep=t_q - t_cut)
         if self.pan_range:
             self._tm_add(pan_align=t_pan - t_up)
         if busy is not None:
             busy.append((t1, t5))
         fallback = container.fallback_pairs([bool(r.get("skipped")) for r in res], uncovered, offsets, self._near)
         return _BlockRecords(self._pair_jobs(res, values, fallback, pool, H * W, C, a.dtype.itemsize, rice),
-                             block_digests, cuts, offsets, adopted, block_quality, near_keys)
+                             block_digests, cuts, offsets, adopted, block_quality, near_keys, run_bounds)
 
     def encode_range(self, frames, first_index, start, stop, inter_frames=True, release=True):
         """[(type, record)] for the frames with global indices [start, stop); frames[i] is global frame
@@ -826,6 +871,8 @@ class ImprovedVideoCompressor:
             results.update(max_error=self.max_error, hold_mode=self.hold_mode)
         if self.error_bounds is not None:
             results.update(error_bounds=True, hold_mode=self.hold_mode)
+        if self.target_psnr is not None:
+            results.update(target_psnr=self.target_psnr, run_bounds=list(self.last_run_bounds))
         if self.bounded_keyframes:
             results["bounded_keyframes"] = sum(1 for ty, _ in records if ty == KEY_NEAR)
         if self.scene_cuts:
