@@ -966,13 +966,10 @@ struct HoldCall {
 static int temporal_hold_impl(rbf_ctx *ctx, const HoldCall &c)
 {
     if (int r = set_device(ctx)) return r;
+    const PackedBlock blk{c.width, c.height, c.channels, c.sample_bytes, c.frame_stride_bytes};
     const uint32_t sample_bytes = c.sample_bytes, channels = c.channels, nframes = c.nframes, max_error = c.max_error;
-    const uint64_t frame_stride_bytes = c.frame_stride_bytes;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{c.width, c.height, (uint64_t)c.width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, nframes, rules)) return r;
+    const uint64_t frame_stride_bytes = c.frame_stride_bytes, n = blk.n();
+    if (int r = check_block_shape(blk, nframes)) return r;
     if (c.map) {
         if (!c.bounds_dev) return fail(RBF_EINVAL, "null bounds_dev");
         if ((uintptr_t)c.bounds_dev % sample_bytes) return fail(RBF_EINVAL, "bounds misaligned for %u-byte samples", sample_bytes);
@@ -981,73 +978,49 @@ static int temporal_hold_impl(rbf_ctx *ctx, const HoldCall &c)
         if (max_error >> (8 * sample_bytes)) return fail(RBF_ERANGE, "max_error %u does not fit a %u-bit sample", max_error, 8 * sample_bytes);
         if (max_error == 0 || nframes < 2) return RBF_OK;         // y = x
     }
-    if (!c.frames_dev) return fail(RBF_EINVAL, "null device pointer");
-    if ((uintptr_t)c.frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)c.width * c.height, frame_bytes = n * pixel;
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (!c.frames_dev) return fail(RBF_EINVAL, "null pointer");
+    if (int r = check_block_at(blk, nframes, c.frames_dev)) return r;
     // lane tiles of 16 pixels through 16-byte accesses (look-ahead: 8 pixels, 8-byte accesses) where the layout allows them -- the frames'
     // base and stride, and the bound frame's base --, the per-pixel kernel for everything else
-    const uint32_t lane_px = c.lookahead ? LA_LANE_PIXELS : HOLD_LANE_PIXELS, align = c.lookahead ? 8 : 16;
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)c.frames_dev % align == 0 && frame_stride_bytes % align == 0 &&
-                     (!c.map || (uintptr_t)c.bounds_dev % align == 0);
-    const uint64_t lanes = vec ? n / lane_px : 0, first_px = lanes * lane_px;
-    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
-    if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    const bool vec = !ctx->knobs.force_generic && lanes_aligned(c.lookahead ? 8 : 16, (uintptr_t)c.frames_dev, (uintptr_t)c.bounds_dev, frame_stride_bytes);
+    const LaneSplit sp = split_lanes(n, c.lookahead ? LA_LANE_PIXELS : HOLD_LANE_PIXELS, WG_THREADS, WG_THREADS, WG_WAVES, vec);
+    if (!sp.fits()) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
     const uint64_t bits_stride = (n + 7) / 8;                     // look-ahead, the segment-start bits: a row per frame, a byte per lane tile
-    if (c.lookahead && lanes)
-        if (int r = ctx->hold_bits.reserve((size_t)nframes * bits_stride)) return r;
+    if (c.lookahead && sp.units) { if (int r = ctx->hold_bits.reserve((size_t)nframes * bits_stride)) return r; }
     uint8_t *const frames = (uint8_t *)c.frames_dev, *const bits = ctx->hold_bits.p;
     const uint8_t *const bounds = (const uint8_t *)c.bounds_dev;
-    HoldRuns runs{};
-    uint32_t count = 0;
+    HoldRuns runs{}; uint32_t count = 0;
+    auto go = [&](auto kernel, uint64_t bx, auto... args) {      // `bx` workgroups per run of the flush
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)bx, count), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes, args..., runs);
+    };
     auto flush = [&]() {
         if (!count) return;
         LaunchTimer t(ctx, RBF_K_HOLD);
-        if (lanes) {
-            const dim3 grid((uint32_t)bx_lanes, count), block(WG_THREADS);
-#define RBF_HOLD(S, C)                                                                                                                           \
-    do {                                                                                                                                         \
-        if (!c.lookahead && !c.map)                                                                                                              \
-            hipLaunchKernelGGL((k_temporal_hold<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, runs);        \
-        else if (!c.lookahead)                                                                                                                   \
-            hipLaunchKernelGGL((k_hold_map<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bounds, runs);                \
-        else if (!c.map)                                                                                                                         \
-            hipLaunchKernelGGL((k_temporal_lookahead<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, max_error, bits, bits_stride, runs); \
-        else                                                                                                                                     \
-            hipLaunchKernelGGL((k_lookahead_map<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bounds, bits, bits_stride, runs); \
-        if (c.lookahead)                                                                                                                         \
-            hipLaunchKernelGGL((k_lookahead_fill<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, lanes, bits, bits_stride, runs); \
-    } while (0)
-            if (sample_bytes == 1) { if (channels == 1) RBF_HOLD(uint8_t, 1); else if (channels == 2) RBF_HOLD(uint8_t, 2); else if (channels == 3) RBF_HOLD(uint8_t, 3); else RBF_HOLD(uint8_t, 4); }
-            else { if (channels == 1) RBF_HOLD(uint16_t, 1); else if (channels == 2) RBF_HOLD(uint16_t, 2); else if (channels == 3) RBF_HOLD(uint16_t, 3); else RBF_HOLD(uint16_t, 4); }
-#undef RBF_HOLD
-        }
-        if (first_px < n)
-            by_sample_width(sample_bytes, [&](auto s) {
+        if (sp.units)
+            by_sample_and_channels(sample_bytes, channels, [&](auto s, auto ch) {
                 using S = decltype(s);
-                const dim3 grid((uint32_t)bx_px, count), block(WG_THREADS);
-                if (!c.lookahead && !c.map)
-                    hipLaunchKernelGGL(k_temporal_hold_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, max_error, runs);
-                else if (!c.lookahead)
-                    hipLaunchKernelGGL(k_hold_map_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, bounds, runs);
-                else if (!c.map)
-                    hipLaunchKernelGGL(k_temporal_lookahead_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, max_error, runs);
-                else
-                    hipLaunchKernelGGL(k_lookahead_map_px<S>, grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, bounds, runs);
+                constexpr int C = decltype(ch)::value;
+                if (!c.lookahead && !c.map) go(k_temporal_hold<S, C>, sp.bx_vec, sp.units, max_error);
+                else if (!c.lookahead) go(k_hold_map<S, C>, sp.bx_vec, sp.units, bounds);
+                else if (!c.map) go(k_temporal_lookahead<S, C>, sp.bx_vec, sp.units, max_error, bits, bits_stride);
+                else go(k_lookahead_map<S, C>, sp.bx_vec, sp.units, bounds, bits, bits_stride);
+                if (c.lookahead) go(k_lookahead_fill<S, C>, sp.bx_vec, sp.units, bits, bits_stride);
+            });
+        if (sp.first_px < n)
+            by_sample_width(sample_bytes, [&](auto s) {
+                if (!c.lookahead && !c.map) go(k_temporal_hold_px<decltype(s)>, sp.bx_px, sp.first_px, n, channels, max_error);
+                else if (!c.lookahead) go(k_hold_map_px<decltype(s)>, sp.bx_px, sp.first_px, n, channels, bounds);
+                else if (!c.map) go(k_temporal_lookahead_px<decltype(s)>, sp.bx_px, sp.first_px, n, channels, max_error);
+                else go(k_lookahead_map_px<decltype(s)>, sp.bx_px, sp.first_px, n, channels, bounds);
             });
         count = 0;
     };
-    // the runs: frame 0 and every marked frame start one; a run of one frame has nothing to hold
-    for (uint32_t a = 0; a < nframes;) {
-        uint32_t b = a + 1;
-        while (b < nframes && !(c.run_starts && c.run_starts[b])) ++b;
-        if (b - a >= 2) {
-            runs.first[count] = a; runs.len[count] = b - a;
-            if (++count == HOLD_MAX_RUNS) flush();
-        }
-        a = b;
-    }
+    for_each_run(c.run_starts, nframes, [&](uint32_t first, uint32_t len) {
+        if (len < 2) return 0;                                    // a run of one frame has nothing to hold
+        runs.first[count] = first; runs.len[count] = len;
+        if (++count == HOLD_MAX_RUNS) flush();
+        return 0;
+    });
     flush();
     HIP_TRY(hipGetLastError());
     return RBF_OK;
@@ -1721,42 +1694,33 @@ int rbf_cut_stats(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_by
                   uint32_t tolerance, uint64_t *stats_dev)
 {
     if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, nframes, rules)) return r;
+    const PackedBlock blk{width, height, channels, sample_bytes, frame_stride_bytes};
+    if (int r = check_block_shape(blk, nframes)) return r;
     if (tolerance >> (8 * sample_bytes)) return fail(RBF_ERANGE, "tolerance %u does not fit a %u-bit sample", tolerance, 8 * sample_bytes);
     if (nframes < 2) return RBF_OK;                               // no pair
-    if (!frames_dev || !stats_dev) return fail(RBF_EINVAL, "null device pointer");
-    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
+    if (!frames_dev || !stats_dev) return fail(RBF_EINVAL, "null pointer");
     if ((uintptr_t)stats_dev % 8) return fail(RBF_EINVAL, "stats_dev must be 8-byte aligned");
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (int r = check_block_at(blk, nframes, frames_dev)) return r;
     // lane tiles of 16 pixels through 16-byte loads where the layout allows them, the per-pixel kernel for everything else
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
-    const uint64_t lanes = vec ? n / CUT_LANE_PIXELS : 0, first_px = lanes * CUT_LANE_PIXELS;
-    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
-    if (bx_lanes > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
+    const uint64_t n = blk.n();
+    const bool vec = !ctx->knobs.force_generic && lanes_aligned(16, (uintptr_t)frames_dev, frame_stride_bytes);
+    const LaneSplit sp = split_lanes(n, CUT_LANE_PIXELS, WG_THREADS, WG_THREADS, WG_WAVES, vec);
+    if (!sp.fits()) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
     const uint32_t pairs = nframes - 1;
-    const uint64_t rows = (bx_lanes + bx_px) * WG_WAVES;          // a row of three sums per wave and pair; every row is written by every call
-    if (int r = ctx->cut_partials.reserve((size_t)pairs * rows * CUT_STATS * 4)) return r;
+    if (int r = ctx->cut_partials.reserve((size_t)pairs * sp.rows * CUT_STATS * 4)) return r;      // a row of three sums per wave and pair; every row is written by every call
     const uint8_t *const frames = (const uint8_t *)frames_dev;
     uint32_t *const partials = ctx->cut_partials.p;
-    if (lanes) {
-        const dim3 grid((uint32_t)bx_lanes), block(WG_THREADS);
-#define RBF_CUT(S, C) hipLaunchKernelGGL((k_cut_stats<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, nframes, lanes, width, tolerance, partials, rows)
-        if (sample_bytes == 1) { if (channels == 1) RBF_CUT(uint8_t, 1); else if (channels == 2) RBF_CUT(uint8_t, 2); else if (channels == 3) RBF_CUT(uint8_t, 3); else RBF_CUT(uint8_t, 4); }
-        else { if (channels == 1) RBF_CUT(uint16_t, 1); else if (channels == 2) RBF_CUT(uint16_t, 2); else if (channels == 3) RBF_CUT(uint16_t, 3); else RBF_CUT(uint16_t, 4); }
-#undef RBF_CUT
-    }
-    if (first_px < n)
-        by_sample_width(sample_bytes, [&](auto s) {
-            hipLaunchKernelGGL(k_cut_stats_px<decltype(s)>, dim3((uint32_t)bx_px), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes,
-                               nframes, first_px, n, width, channels, tolerance, partials, rows, bx_lanes * WG_WAVES);
+    if (sp.units)
+        by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) {
+            hipLaunchKernelGGL((k_cut_stats<decltype(s), decltype(c)::value>), dim3((uint32_t)sp.bx_vec), dim3(WG_THREADS), 0, ctx->stream, frames,
+                               frame_stride_bytes, nframes, sp.units, width, tolerance, partials, sp.rows);
         });
-    hipLaunchKernelGGL(k_cut_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, partials, rows, stats_dev);
+    if (sp.first_px < n)
+        by_sample_width(sample_bytes, [&](auto s) {
+            hipLaunchKernelGGL(k_cut_stats_px<decltype(s)>, dim3((uint32_t)sp.bx_px), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes,
+                               nframes, sp.first_px, n, width, channels, tolerance, partials, sp.rows, sp.tail_row_base);
+        });
+    hipLaunchKernelGGL(k_cut_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, partials, sp.rows, stats_dev);
     HIP_TRY(hipGetLastError());
     return RBF_OK;
 }
@@ -1769,55 +1733,37 @@ int rbf_error_stats(rbf_ctx *ctx, const void *a_dev, uint64_t a_stride_bytes, co
 {
     static_assert(sizeof(ErrorRow) == sizeof(rbf_error_row) && sizeof(rbf_error_row) == 32, "the kernels write the ABI's rows");
     if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    for (const uint64_t stride : {a_stride_bytes, b_stride_bytes}) {
-        const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, stride};
-        if (int r = check_layout(l, nframes, rules)) return r;
-    }
+    const PackedBlock blk_a{width, height, channels, sample_bytes, a_stride_bytes}, blk_b{width, height, channels, sample_bytes, b_stride_bytes};
+    if (int r = check_block_shape(blk_a, nframes)) return r;
+    if (int r = check_block_shape(blk_b, nframes)) return r;
     if (!bounds_dev && bound >> (8 * sample_bytes)) return fail(RBF_ERANGE, "bound %u does not fit a %u-bit sample", bound, 8 * sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    const uint64_t n = blk_a.n();
     if (n * channels > 0x80000000ull) return fail(RBF_ERANGE, "frame of %llu samples is too large", (unsigned long long)(n * channels));
     if (nframes == 0) return RBF_OK;
     if (!a_dev || !b_dev || !rows_host) return fail(RBF_EINVAL, "null pointer");
-    if ((uintptr_t)a_dev % sample_bytes || (uintptr_t)b_dev % sample_bytes || (uintptr_t)bounds_dev % sample_bytes)
-        return fail(RBF_EINVAL, "blocks or bounds misaligned for %u-byte samples", sample_bytes);
-    if (nframes > 1 && (a_stride_bytes < frame_bytes || b_stride_bytes < frame_bytes))
-        return fail(RBF_EINVAL, "frame stride smaller than a frame of %llu bytes", (unsigned long long)frame_bytes);
+    if (int r = check_block_at(blk_a, nframes, a_dev, true)) return r;        // (a single frame has no stride to look at)
+    if (int r = check_block_at(blk_b, nframes, b_dev, true)) return r;
+    if ((uintptr_t)bounds_dev % sample_bytes) return fail(RBF_EINVAL, "bounds misaligned for %u-byte samples", sample_bytes);
     // lane tiles of 16 pixels through 16-byte loads where every base and stride allows them, the per-pixel kernel for everything else
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)a_dev % 16 == 0 && (uintptr_t)b_dev % 16 == 0 && (uintptr_t)bounds_dev % 16 == 0 &&
-                     (nframes == 1 || (a_stride_bytes % 16 == 0 && b_stride_bytes % 16 == 0));
-    const uint64_t lanes = vec ? n / ERR_LANE_PIXELS : 0, first_px = lanes * ERR_LANE_PIXELS;
-    const uint64_t bx_lanes = (lanes + WG_THREADS - 1) / WG_THREADS, bx_px = (n - first_px + WG_THREADS - 1) / WG_THREADS;
-    const uint64_t rows = (bx_lanes + bx_px) * WG_WAVES;          // a row per wave and frame; every row is written by every call
-    if (int r = ctx->err_partials.reserve((size_t)nframes * rows * ERR_WORDS * 4)) return r;
+    const bool vec = !ctx->knobs.force_generic && lanes_aligned(16, (uintptr_t)a_dev, (uintptr_t)b_dev, (uintptr_t)bounds_dev, nframes == 1 ? 0 : a_stride_bytes | b_stride_bytes);
+    const LaneSplit sp = split_lanes(n, ERR_LANE_PIXELS, WG_THREADS, WG_THREADS, WG_WAVES, vec);     // (at most 2^31 samples: it fits)
+    if (int r = ctx->err_partials.reserve((size_t)nframes * sp.rows * ERR_WORDS * 4)) return r;      // a row per wave and frame; every row is written by every call
     if (int r = ctx->err_rows.reserve((size_t)nframes * sizeof(ErrorRow))) return r;
     const uint8_t *const a = (const uint8_t *)a_dev, *const b = (const uint8_t *)b_dev, *const bounds = (const uint8_t *)bounds_dev;
     uint32_t *const partials = ctx->err_partials.p;
-    if (lanes) {
-        const dim3 grid((uint32_t)bx_lanes), block(WG_THREADS);
-#define RBF_ERR(S, C)                                                                                                                            \
-    do {                                                                                                                                         \
-        if (bounds)                                                                                                                              \
-            hipLaunchKernelGGL((k_error_stats<S, C, true>), grid, block, 0, ctx->stream, a, a_stride_bytes, b, b_stride_bytes, nframes, lanes, bounds, bound, partials, rows); \
-        else                                                                                                                                     \
-            hipLaunchKernelGGL((k_error_stats<S, C, false>), grid, block, 0, ctx->stream, a, a_stride_bytes, b, b_stride_bytes, nframes, lanes, bounds, bound, partials, rows); \
-    } while (0)
-        if (sample_bytes == 1) { if (channels == 1) RBF_ERR(uint8_t, 1); else if (channels == 2) RBF_ERR(uint8_t, 2); else if (channels == 3) RBF_ERR(uint8_t, 3); else RBF_ERR(uint8_t, 4); }
-        else { if (channels == 1) RBF_ERR(uint16_t, 1); else if (channels == 2) RBF_ERR(uint16_t, 2); else if (channels == 3) RBF_ERR(uint16_t, 3); else RBF_ERR(uint16_t, 4); }
-#undef RBF_ERR
-    }
-    if (first_px < n)
-        by_sample_width(sample_bytes, [&](auto s) {
-            hipLaunchKernelGGL(k_error_stats_px<decltype(s)>, dim3((uint32_t)bx_px), dim3(WG_THREADS), 0, ctx->stream, a, a_stride_bytes, b,
-                               b_stride_bytes, nframes, first_px, n, channels, bounds, bound, partials, rows, bx_lanes * WG_WAVES);
+    if (sp.units)
+        by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) {
+            by_value<0, 1>(bounds != nullptr, [&](auto map) {
+                hipLaunchKernelGGL((k_error_stats<decltype(s), decltype(c)::value, decltype(map)::value != 0>), dim3((uint32_t)sp.bx_vec), dim3(WG_THREADS), 0, ctx->stream,
+                                   a, a_stride_bytes, b, b_stride_bytes, nframes, sp.units, bounds, bound, partials, sp.rows);
+            });
         });
-    hipLaunchKernelGGL(k_error_reduce, dim3(nframes), dim3(WG_THREADS), 0, ctx->stream, partials, rows, (ErrorRow *)ctx->err_rows.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rows_host, ctx->err_rows.p, (size_t)nframes * sizeof(ErrorRow), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RBF_OK;
+    if (sp.first_px < n)
+        by_sample_width(sample_bytes, [&](auto s) {
+            hipLaunchKernelGGL(k_error_stats_px<decltype(s)>, dim3((uint32_t)sp.bx_px), dim3(WG_THREADS), 0, ctx->stream, a, a_stride_bytes, b,
+                               b_stride_bytes, nframes, sp.first_px, n, channels, bounds, bound, partials, sp.rows, sp.tail_row_base);
+        });
+    return fold_rows_to_host(ctx, k_error_reduce, nframes, (ErrorRow *)ctx->err_rows.p, rows_host, partials, sp.rows);
 }
 
 // ---- hold sweep: what every candidate bound would do to every run of a block (rbf_kernels_sweep.h); read-only on the block, blocks
@@ -1830,11 +1776,8 @@ int rbf_hold_sweep(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_b
     static_assert(sizeof(SweepRow) == sizeof(rbf_sweep_row) && sizeof(rbf_sweep_row) == 24, "the kernels write the ABI's rows");
     static_assert(SWEEP_MAX_RUN * 4 * 255 * 255 <= 0xFFFFFFFFu / 64, "a wave's sse of a run fits 32 bits");
     if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, nframes, rules)) return r;
+    const PackedBlock blk{width, height, channels, sample_bytes, frame_stride_bytes};
+    if (int r = check_block_shape(blk, nframes)) return r;
     if (ncandidates < 1 || ncandidates > SWEEP_MAX_CANDIDATES) return fail(RBF_EINVAL, "ncandidates must be 1..%u, got %u", SWEEP_MAX_CANDIDATES, ncandidates);
     if (!candidates) return fail(RBF_EINVAL, "null candidates");
     uint64_t cands = 0;
@@ -1846,64 +1789,40 @@ int rbf_hold_sweep(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_b
     }
     if (nframes == 0) return RBF_OK;
     if (!frames_dev || !rows_host) return fail(RBF_EINVAL, "null pointer");
-    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
-    // the runs: frame 0 and every marked frame start one; a run of one frame keeps its rows (of zeros)
-    HoldRuns runs{};
-    uint32_t count = 0;
-    for (uint32_t a = 0; a < nframes;) {
-        uint32_t b = a + 1;
-        while (b < nframes && !(run_starts && run_starts[b])) ++b;
-        if (count == HOLD_MAX_RUNS) return fail(RBF_ERANGE, "more than %u runs", HOLD_MAX_RUNS);
-        if (b - a > SWEEP_MAX_RUN) return fail(RBF_ERANGE, "run of %u frames at frame %u: at most %u", b - a, a, SWEEP_MAX_RUN);
-        runs.first[count] = a; runs.len[count] = b - a;
-        ++count;
-        a = b;
-    }
+    if (int r = check_block_at(blk, nframes, frames_dev)) return r;
+    HoldRuns runs{}; uint32_t count = 0;                          // a run of one frame keeps its rows (of zeros)
+    if (int r = for_each_run(run_starts, nframes, [&](uint32_t first, uint32_t len) {
+            if (count == HOLD_MAX_RUNS) return fail(RBF_ERANGE, "more than %u runs", HOLD_MAX_RUNS);
+            if (len > SWEEP_MAX_RUN) return fail(RBF_ERANGE, "run of %u frames at frame %u: at most %u", len, first, SWEEP_MAX_RUN);
+            runs.first[count] = first; runs.len[count++] = len;
+            return 0;
+        })) return r;
     // workgroup tiles through 16-byte loads where the layout allows them, the per-pixel kernel for everything else; more than four
-    // candidates: two halves of a workgroup share a tile of half the size
+    // candidates: two halves of a workgroup share a tile of half the size.  The lane unit is the tile, one to a workgroup
+    const uint64_t n = blk.n();
     const uint32_t groups = ncandidates > SWEEP_GROUP ? 2 : 1, tile = WG_THREADS / groups;
-    const bool vec = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
-    const uint64_t tiles = vec ? n / tile : 0, first_px = tiles * tile;
-    const uint64_t bx_px = (n - first_px + tile - 1) / tile;
-    if (tiles > 0x7FFFFFFFull || bx_px > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
-    const uint64_t rows = (tiles + bx_px) * (tile / WAVE);        // a row per wave, run and candidate; every row is written by every call
+    const bool vec = !ctx->knobs.force_generic && lanes_aligned(16, (uintptr_t)frames_dev, frame_stride_bytes);
+    const LaneSplit sp = split_lanes(n, tile, 1, tile, tile / WAVE, vec);
+    if (!sp.fits()) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
     const uint32_t cells = count * ncandidates;
-    if (int r = ctx->sweep_partials.reserve((size_t)cells * rows * SWEEP_WORDS * 4)) return r;
+    if (int r = ctx->sweep_partials.reserve((size_t)cells * sp.rows * SWEEP_WORDS * 4)) return r;      // a row per wave, run and candidate; every row is written by every call
     if (int r = ctx->sweep_rows.reserve((size_t)cells * sizeof(SweepRow))) return r;
     const uint8_t *const frames = (const uint8_t *)frames_dev;
     uint32_t *const partials = ctx->sweep_partials.p;
-    if (tiles) {
-        const dim3 grid((uint32_t)tiles, count), block(WG_THREADS);
-#define RBF_SWEEP(S, C)                                                                                                                          \
-    do {                                                                                                                                         \
-        if (lookahead)                                                                                                                           \
-            hipLaunchKernelGGL((k_hold_sweep<S, C, true>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, groups, cands, ncandidates, partials, rows, runs); \
-        else                                                                                                                                     \
-            hipLaunchKernelGGL((k_hold_sweep<S, C, false>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, groups, cands, ncandidates, partials, rows, runs); \
-    } while (0)
-        if (sample_bytes == 1) { if (channels == 1) RBF_SWEEP(uint8_t, 1); else if (channels == 2) RBF_SWEEP(uint8_t, 2); else if (channels == 3) RBF_SWEEP(uint8_t, 3); else RBF_SWEEP(uint8_t, 4); }
-        else { if (channels == 1) RBF_SWEEP(uint16_t, 1); else if (channels == 2) RBF_SWEEP(uint16_t, 2); else if (channels == 3) RBF_SWEEP(uint16_t, 3); else RBF_SWEEP(uint16_t, 4); }
-#undef RBF_SWEEP
-    }
-    if (first_px < n)
-        by_sample_width(sample_bytes, [&](auto s) {
-            using S = decltype(s);
-            const dim3 grid((uint32_t)bx_px, count), block(WG_THREADS);
-            if (lookahead)
-                hipLaunchKernelGGL((k_hold_sweep_px<S, true>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, groups,
-                                   cands, ncandidates, partials, rows, tiles * (tile / WAVE), runs);
-            else
-                hipLaunchKernelGGL((k_hold_sweep_px<S, false>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, first_px, n, channels, groups,
-                                   cands, ncandidates, partials, rows, tiles * (tile / WAVE), runs);
-        });
-    hipLaunchKernelGGL(k_sweep_reduce, dim3(cells), dim3(WG_THREADS), 0, ctx->stream, partials, rows, (SweepRow *)ctx->sweep_rows.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rows_host, ctx->sweep_rows.p, (size_t)cells * sizeof(SweepRow), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RBF_OK;
+    by_value<0, 1>(lookahead != 0, [&](auto la) {
+        constexpr bool LA = decltype(la)::value != 0;
+        if (sp.units)
+            by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) {
+                hipLaunchKernelGGL((k_hold_sweep<decltype(s), decltype(c)::value, LA>), dim3((uint32_t)sp.bx_vec, count), dim3(WG_THREADS), 0, ctx->stream, frames,
+                                   frame_stride_bytes, groups, cands, ncandidates, partials, sp.rows, runs);
+            });
+        if (sp.first_px < n)
+            by_sample_width(sample_bytes, [&](auto s) {
+                hipLaunchKernelGGL((k_hold_sweep_px<decltype(s), LA>), dim3((uint32_t)sp.bx_px, count), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes,
+                                   sp.first_px, n, channels, groups, cands, ncandidates, partials, sp.rows, sp.tail_row_base, runs);
+            });
+    });
+    return fold_rows_to_host(ctx, k_sweep_reduce, cells, (SweepRow *)ctx->sweep_rows.p, rows_host, partials, sp.rows);
 }
 
 // ---- pan alignment: the global integer shift of every pair and the roll that makes the block still (rbf_kernels_pan.h)
@@ -1913,26 +1832,20 @@ int rbf_pan_search(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_b
 {
     static_assert(sizeof(PanRow) == sizeof(rbf_pan_stat) && sizeof(rbf_pan_stat) == 40, "the kernels write the ABI's rows");
     if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, nframes, rules)) return r;
+    const PackedBlock blk{width, height, channels, sample_bytes, frame_stride_bytes};
+    if (int r = check_block_shape(blk, nframes)) return r;
     if (range < 1 || range > (uint32_t)PAN_MAX_RANGE) return fail(RBF_EINVAL, "range must be 1..%d, got %u", PAN_MAX_RANGE, range);
     if (width <= 2 * range || height <= 2 * range)
         return fail(RBF_EINVAL, "a frame of %ux%u has no grid point for range %u: width and height must exceed 2 * range", width, height, range);
     if (tolerance >> (8 * sample_bytes)) return fail(RBF_EINVAL, "tolerance %u does not fit a %u-bit sample", tolerance, 8 * sample_bytes);
     if (nframes < 2) return RBF_OK;                               // no pair
     if (!frames_dev || !out) return fail(RBF_EINVAL, "null pointer");
-    if ((uintptr_t)frames_dev % sample_bytes) return fail(RBF_EINVAL, "frames misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (int r = check_block_at(blk, nframes, frames_dev)) return r;
     const uint32_t pairs = nframes - 1;
     if (pairs > 65535) return fail(RBF_ERANGE, "at most 65536 frames per call, got %u", nframes);
     const uint32_t ngx = (width - 2 * range + PAN_GRID - 1) / PAN_GRID, ngy = (height - 2 * range + PAN_GRID - 1) / PAN_GRID;
     const uint32_t tiles_x = (ngx + PAN_TX - 1) / PAN_TX, tiles_y = (ngy + PAN_TY - 1) / PAN_TY;
-    const uint64_t tiles = (uint64_t)tiles_x * tiles_y, nd = 2 * range + 1;
+    const uint64_t n = blk.n(), tiles = (uint64_t)tiles_x * tiles_y, nd = 2 * range + 1;
     const uint64_t bx = (n + WG_THREADS - 1) / WG_THREADS, rows = bx * WG_WAVES;
     if (tiles > 0x7FFFFFFFull || bx > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
     if (int r = ctx->pan_partials.reserve((size_t)pairs * tiles * nd * nd * 4)) return r;
@@ -1944,31 +1857,22 @@ int rbf_pan_search(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_stride_b
     if (run_starts)
         for (uint32_t t = 1; t < nframes; ++t) starts[t] = run_starts[t] ? 1 : 0;
     HIP_TRY(hipMemcpyAsync(ctx->pan_runs.p, starts.data(), nframes, hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t *const frames = (const uint8_t *)frames_dev;
+    const uint8_t *const frames = (const uint8_t *)frames_dev, *const runs = ctx->pan_runs.p;
     PanRow *const prow = (PanRow *)ctx->pan_rows.p;
     const uint32_t lds = pan_sad_lds_bytes(range, sample_bytes);
-    {
-        const dim3 grid((uint32_t)tiles, pairs), block(WG_THREADS);
-#define RBF_PAN_SAD(S, RM) hipLaunchKernelGGL((k_pan_sad<S, RM>), grid, block, lds, ctx->stream, frames, frame_stride_bytes, width, height, channels, range, ngx, ngy, tiles_x, ctx->pan_runs.p, ctx->pan_partials.p)
-        by_sample_width(sample_bytes, [&](auto s) {
-            using S = decltype(s);
-            if (range <= 8) RBF_PAN_SAD(S, 8); else if (range <= 16) RBF_PAN_SAD(S, 16); else RBF_PAN_SAD(S, 32);
+    by_sample_width(sample_bytes, [&](auto s) {
+        by_value<8, 16, 32>(range <= 8 ? 8 : range <= 16 ? 16 : 32, [&](auto rmax) {
+            hipLaunchKernelGGL((k_pan_sad<decltype(s), decltype(rmax)::value>), dim3((uint32_t)tiles, pairs), dim3(WG_THREADS), lds, ctx->stream, frames, frame_stride_bytes,
+                               width, height, channels, range, ngx, ngy, tiles_x, runs, ctx->pan_partials.p);
         });
-#undef RBF_PAN_SAD
-    }
-    hipLaunchKernelGGL(k_pan_pick, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, ctx->pan_partials.p, (uint32_t)tiles, range, ctx->pan_runs.p, prow);
-    {
-        const dim3 grid((uint32_t)bx, pairs), block(WG_THREADS);
-#define RBF_PAN_MOV(S, C) hipLaunchKernelGGL((k_pan_moving<S, C>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, width, height, tolerance, ctx->pan_runs.p, prow, ctx->pan_moving.p, rows)
-        if (sample_bytes == 1) { if (channels == 1) RBF_PAN_MOV(uint8_t, 1); else if (channels == 2) RBF_PAN_MOV(uint8_t, 2); else if (channels == 3) RBF_PAN_MOV(uint8_t, 3); else RBF_PAN_MOV(uint8_t, 4); }
-        else { if (channels == 1) RBF_PAN_MOV(uint16_t, 1); else if (channels == 2) RBF_PAN_MOV(uint16_t, 2); else if (channels == 3) RBF_PAN_MOV(uint16_t, 3); else RBF_PAN_MOV(uint16_t, 4); }
-#undef RBF_PAN_MOV
-    }
-    hipLaunchKernelGGL(k_pan_moving_reduce, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, ctx->pan_moving.p, rows, ctx->pan_runs.p, prow);
-    HIP_TRY(hipGetLastError());
-    if (int r = ctx->pan_host.reserve_rows(pairs)) return r;      // (out is written only by a call that succeeded)
-    HIP_TRY(hipMemcpyAsync(ctx->pan_host.rows.data(), prow, (size_t)pairs * sizeof(PanRow), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    });
+    hipLaunchKernelGGL(k_pan_pick, dim3(pairs), dim3(WG_THREADS), 0, ctx->stream, ctx->pan_partials.p, (uint32_t)tiles, range, runs, prow);
+    by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) {
+        hipLaunchKernelGGL((k_pan_moving<decltype(s), decltype(c)::value>), dim3((uint32_t)bx, pairs), dim3(WG_THREADS), 0, ctx->stream, frames, frame_stride_bytes,
+                           width, height, tolerance, runs, prow, ctx->pan_moving.p, rows);
+    });
+    if (int r = ctx->pan_host.reserve_rows(pairs)) return r;      // (the rows pass through it: out is written only by a call that succeeded)
+    if (int r = fold_rows_to_host(ctx, k_pan_moving_reduce, pairs, prow, ctx->pan_host.rows.data(), ctx->pan_moving.p, rows, runs)) return r;
     memcpy(out, ctx->pan_host.rows.data(), (size_t)pairs * sizeof(PanRow));
     return RBF_OK;
 }
@@ -1983,8 +1887,7 @@ int rbf_roll_frames(rbf_ctx *ctx, void *frames_dev, uint64_t frame_stride_bytes,
     if (row_bytes > 0x7FFFFFFFull) return fail(RBF_ERANGE, "a row of %llu bytes is too long", (unsigned long long)row_bytes);
     if (nframes == 0) return RBF_OK;
     if (!frames_dev || !offsets) return fail(RBF_EINVAL, "null pointer");
-    if (nframes > 1 && frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (int r = check_frame_stride(frame_stride_bytes, frame_bytes, nframes, true)) return r;
     const bool vec = !ctx->knobs.force_generic && row_bytes % 16 == 0;
     const uint64_t per_thread = vec ? 16 : 1, bx = (frame_bytes + per_thread * WG_THREADS - 1) / (per_thread * WG_THREADS);
     if (bx > 0x7FFFFFFFull) return fail(RBF_ERANGE, "frame of %llu bytes is too large", (unsigned long long)frame_bytes);
@@ -2029,11 +1932,9 @@ int rbf_frame_view_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_st
                          void *out_dev, uint64_t capacity_bytes)
 {
     if (int r = set_device(ctx)) return r;
-    const uint32_t pixel = channels * sample_bytes;
-    const FrameLayout l{width, height, (uint64_t)width * pixel, pixel, sample_bytes, frame_stride_bytes};
-    LayoutRules rules;
-    rules.samples = channels; rules.channels = true;
-    if (int r = check_layout(l, count, rules)) return r;
+    const PackedBlock blk{width, height, channels, sample_bytes, frame_stride_bytes};
+    const uint32_t pixel = blk.pixel();
+    if (int r = check_block_shape(blk, count)) return r;
     if (!view_scale_ok(scale)) return fail(RBF_EINVAL, "scale must be 1, 2, 4 or 8, got %u", scale);
     if (roi_w == 0 || roi_h == 0) return fail(RBF_EINVAL, "empty region %ux%u", roi_w, roi_h);
     if ((uint64_t)x0 + roi_w > width || (uint64_t)y0 + roi_h > height)
@@ -2042,17 +1943,16 @@ int rbf_frame_view_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_st
     if (!frames_dev || !frame_index || !out_dev) return fail(RBF_EINVAL, "null pointer");
     if ((uintptr_t)frames_dev % sample_bytes || (uintptr_t)out_dev % sample_bytes)
         return fail(RBF_EINVAL, "frames or views misaligned for %u-byte samples", sample_bytes);
-    const uint64_t n = (uint64_t)width * height, frame_bytes = n * pixel;
+    const uint64_t n = blk.n(), frame_bytes = blk.frame_bytes();
     if (frame_bytes / pixel != n || frame_bytes >> 48) return fail(RBF_ERANGE, "frame of %llu pixels is too large", (unsigned long long)n);
     if ((uint64_t)width * pixel > 0x7FFFFFFFull) return fail(RBF_ERANGE, "a row of %llu bytes is too long", (unsigned long long)width * pixel);
-    if (frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (int r = check_frame_stride(frame_stride_bytes, frame_bytes, count, false)) return r;
     for (uint32_t i = 1; i < count; ++i)
         if (frame_index[i] <= frame_index[i - 1])                 // (a frame listed twice would be viewed twice: ask for it once)
             return fail(RBF_EINVAL, "frame indices must ascend: %u after %u", frame_index[i], frame_index[i - 1]);
     const uint32_t last = frame_index[count - 1];
     if (frame_stride_bytes >> 48 || (uint64_t)last * frame_stride_bytes >> 62) return fail(RBF_ERANGE, "frame %u at stride %llu is out of reach", last, (unsigned long long)frame_stride_bytes);
-    const bool aligned16 = !ctx->knobs.force_generic && (uintptr_t)frames_dev % 16 == 0 && frame_stride_bytes % 16 == 0;
+    const bool aligned16 = !ctx->knobs.force_generic && lanes_aligned(16, (uintptr_t)frames_dev, frame_stride_bytes);
     const ViewPlan p = view_plan(width, pixel, x0, roi_w, roi_h, scale, aligned16);
     const uint64_t view_bytes = (uint64_t)p.out_w * p.out_h * pixel, need = view_bytes * count;
     if (capacity_bytes < need)
@@ -2078,25 +1978,22 @@ int rbf_frame_view_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_st
         const uint32_t cnt = count - f0 < MAX_Y ? count - f0 : MAX_Y;
         const uint32_t *const index = ctx->view_index.p + f0;
         uint8_t *const out = (uint8_t *)out_dev + (uint64_t)f0 * view_bytes;
-        if (bx_wide) {
-            const dim3 grid((uint32_t)bx_wide, cnt), block(WG_THREADS);
-#define RBF_VIEW(S, C, K) hipLaunchKernelGGL((k_frame_view<S, C, K>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, index, row_bytes, roi_off, p.tiles_x, p.wide_rows, out, view_bytes, out_row_bytes)
-#define RBF_VIEW_C(S, K) do { if (channels == 1) RBF_VIEW(S, 1, K); else if (channels == 2) RBF_VIEW(S, 2, K); else if (channels == 3) RBF_VIEW(S, 3, K); else RBF_VIEW(S, 4, K); } while (0)
-#define RBF_VIEW_S(S) do { if (scale == 1) RBF_VIEW_C(S, 1); else if (scale == 2) RBF_VIEW_C(S, 2); else if (scale == 4) RBF_VIEW_C(S, 4); else RBF_VIEW_C(S, 8); } while (0)
-            if (sample_bytes == 1) RBF_VIEW_S(uint8_t); else RBF_VIEW_S(uint16_t);
-#undef RBF_VIEW_S
-#undef RBF_VIEW_C
-#undef RBF_VIEW
-        }
+        if (bx_wide)
+            by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) {
+                by_value<1, 2, 4, 8>(scale, [&](auto k) {
+                    hipLaunchKernelGGL((k_frame_view<decltype(s), decltype(c)::value, decltype(k)::value>), dim3((uint32_t)bx_wide, cnt), dim3(WG_THREADS), 0,
+                                       ctx->stream, frames, frame_stride_bytes, index, row_bytes, roi_off, p.tiles_x, p.wide_rows, out, view_bytes, out_row_bytes);
+                });
+            });
         for (int r = 0; r < 2; ++r) {
             if (!bx_px[r]) continue;
             const uint32_t *const q = rects[r];
-            const dim3 grid((uint32_t)bx_px[r], cnt), block(WG_THREADS);
-#define RBF_VIEW_PX(S, K) hipLaunchKernelGGL((k_frame_view_px<S, K>), grid, block, 0, ctx->stream, frames, frame_stride_bytes, index, width, channels, x0, y0, roi_w, roi_h, p.out_w, q[0], q[1], q[2], q[3], out, view_bytes)
-#define RBF_VIEW_PX_S(S) do { if (scale == 1) RBF_VIEW_PX(S, 1); else if (scale == 2) RBF_VIEW_PX(S, 2); else if (scale == 4) RBF_VIEW_PX(S, 4); else RBF_VIEW_PX(S, 8); } while (0)
-            if (sample_bytes == 1) RBF_VIEW_PX_S(uint8_t); else RBF_VIEW_PX_S(uint16_t);
-#undef RBF_VIEW_PX_S
-#undef RBF_VIEW_PX
+            by_sample_width(sample_bytes, [&](auto s) {
+                by_value<1, 2, 4, 8>(scale, [&](auto k) {
+                    hipLaunchKernelGGL((k_frame_view_px<decltype(s), decltype(k)::value>), dim3((uint32_t)bx_px[r], cnt), dim3(WG_THREADS), 0, ctx->stream, frames,
+                                       frame_stride_bytes, index, width, channels, x0, y0, roi_w, roi_h, p.out_w, q[0], q[1], q[2], q[3], out, view_bytes);
+                });
+            });
         }
     }
     HIP_TRY(hipGetLastError());
@@ -2112,8 +2009,7 @@ int rbf_frame_digest_batch(rbf_ctx *ctx, const void *frames_dev, uint64_t frame_
     if (frame_bytes == 0) return fail(RBF_EINVAL, "frame_bytes must be >= 1: an empty frame has no resident bytes to hash");
     if (!frames_dev || !digests_dev) return fail(RBF_EINVAL, "null device pointer");
     if ((uintptr_t)digests_dev % 8) return fail(RBF_EINVAL, "digests_dev must be 8-byte aligned");
-    if (nframes > 1 && frame_stride_bytes < frame_bytes)
-        return fail(RBF_EINVAL, "frame stride %llu smaller than a frame of %llu bytes", (unsigned long long)frame_stride_bytes, (unsigned long long)frame_bytes);
+    if (int r = check_frame_stride(frame_stride_bytes, frame_bytes, nframes, true)) return r;
     const uint32_t levels = fd1_levels(frame_bytes);
     const uint64_t words = fd1_scratch_words(frame_bytes);
     constexpr uint32_t MAX_Y = 65535;                             // frames of one launch (gridDim.y)

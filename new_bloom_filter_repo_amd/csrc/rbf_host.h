@@ -1,14 +1,17 @@
 // rbf_host.h -- what every entry point of rbf_api.hip stands on: the last-error text, the context and its scratch memory, per-kernel
-// timing, the process-wide pixel-index hash table, and the argument checks and launch helpers that several entry points share.
+// timing, the process-wide pixel-index hash table, the Bloom rows' argument checks, and the shared launch helpers: the dispatch on sample type,
+// channels and other template constants, the mask counts, the fold-and-fetch tail.  Frame layouts and block arithmetic: rbf_block_plan.h.
 #pragma once
 #include "rbf_kernels.h"
 #include "rbf_kernels_insert_f64.h"
+#include "rbf_block_plan.h"
 #include "rbf_plan.h"
 
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 // ------------------------------------------------------------------------------------------
@@ -319,37 +322,6 @@ static int check_witness_stride(uint64_t n, uint64_t witness_stride_bytes)
     return RBF_OK;
 }
 
-// How an entry point's frames lie in memory (bytes), and what the entry point asks of that layout.
-struct FrameLayout {
-    uint32_t width, height;
-    uint64_t row_pitch;
-    uint32_t pixel_stride, sample_bytes;
-    uint64_t frame_stride;           // 0: a single frame
-};
-struct LayoutRules {
-    uint32_t samples = 1;            // samples of a pixel the entry point touches: the pixel stride has to hold them
-    bool channels = false;           // `samples` is the caller's channel count: 1..4
-    bool aligned = true;             // pixel stride, row pitch and frame stride are multiples of the sample size
-    uint32_t min_frames = 0, max_frames = 0xFFFFFFFFu;
-    uint32_t max_height = 0;         // 0: any
-};
-
-static int check_layout(const FrameLayout &l, uint32_t nframes, const LayoutRules &r)
-{
-    if (nframes < r.min_frames || nframes > r.max_frames)
-        return fail(RBF_EINVAL, "frame count %u out of range %u..%u", nframes, r.min_frames, r.max_frames);
-    if (l.width == 0 || l.height == 0) return fail(RBF_EINVAL, "empty frame %ux%u", l.width, l.height);
-    if (r.max_height && l.height > r.max_height) return fail(RBF_ERANGE, "at most %u rows, got %u", r.max_height, l.height);
-    if (l.sample_bytes != 1 && l.sample_bytes != 2) return fail(RBF_EINVAL, "sample_bytes must be 1 or 2, got %u", l.sample_bytes);
-    if (r.channels && (r.samples == 0 || r.samples > 4)) return fail(RBF_EINVAL, "channels must be 1..4, got %u", r.samples);
-    if (l.pixel_stride < r.samples * l.sample_bytes || (r.aligned && l.pixel_stride % l.sample_bytes))
-        return fail(RBF_EINVAL, "pixel stride %u incompatible with %u sample(s) of %u bytes", l.pixel_stride, r.samples, l.sample_bytes);
-    if (l.row_pitch < (uint64_t)l.width * l.pixel_stride || (r.aligned && l.row_pitch % l.sample_bytes))
-        return fail(RBF_EINVAL, "row pitch %llu too small or misaligned", (unsigned long long)l.row_pitch);
-    if (r.aligned && l.frame_stride % l.sample_bytes) return fail(RBF_EINVAL, "frame stride misaligned");
-    return RBF_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // shared launches
 // ------------------------------------------------------------------------------------------
@@ -359,6 +331,32 @@ template <class F> static void by_sample_width(uint32_t sample_bytes, F &&f)
 {
     if (sample_bytes == 1) f(uint8_t{});
     else f(uint16_t{});
+}
+
+// Calls f with v as a compile-time constant, v being V or one of Vs; the last of them takes every other v, as the else of an if-ladder does:
+//   by_value<1, 2, 4, 8>(scale, [&](auto k) { hipLaunchKernelGGL((k_x<decltype(k)::value>), ...); });
+template <uint32_t V, uint32_t... Vs, class F> static void by_value(uint32_t v, F &&f)
+{
+    if constexpr (sizeof...(Vs) > 0) { if (v != V) return by_value<Vs...>(v, f); }
+    f(std::integral_constant<uint32_t, V>{});
+}
+
+// ... and with the sample type and the channel count (1..4), what the lane kernels are templated on:
+//   by_sample_and_channels(sample_bytes, channels, [&](auto s, auto c) { hipLaunchKernelGGL((k_x<decltype(s), decltype(c)::value>), ...); });
+template <class F> static void by_sample_and_channels(uint32_t sample_bytes, uint32_t channels, F &&f)
+{
+    by_sample_width(sample_bytes, [&](auto s) { by_value<1, 2, 3, 4>(channels, [&](auto c) { f(s, c); }); });
+}
+
+// The end of a stage that reports to the host: `fold`, a workgroup per row, folds the stage's partial sums into `count` rows on the device
+// (fold(args..., rows_dev)); they are copied to rows_host, and the call waits for them.
+template <class Row, class Kernel, class... Args> static int fold_rows_to_host(rbf_ctx *ctx, Kernel fold, uint32_t count, Row *rows_dev, void *rows_host, Args... args)
+{
+    hipLaunchKernelGGL(fold, dim3(count), dim3(WG_THREADS), 0, ctx->stream, args..., rows_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rows_host, rows_dev, (size_t)count * sizeof(Row), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RBF_OK;
 }
 
 // The set bits of `rows` mask rows of n pixels per 1024-pixel segment (ctx->seg_cnt), their exclusive scan per row (ctx->seg_off)
