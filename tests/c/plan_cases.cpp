@@ -127,7 +127,7 @@ static int show_table(char *line)
 // "batch n cus flags have_ones nframes m_0 ... m_{nframes-1}": a batch in which every frame has its own filter size (0: not coded), as
 // rbf_bloom_encode_batch / rbf_bloom_decode_batch (have_ones = 0) or rbf_encode_gop_finish (1) plan it.  Prints the undivided plan and,
 // when the batch is mixed, its two halves -- each with the conditions under which encode_chunk / decode_chunk (rbf_api.hip) run the
-// halves instead of the whole: encode_split / decode_split.  tests/test_bloom_rows_cpu.py
+// halves instead of the whole: encode_split / decode_split.  tests/test_bloom_rows_cpu.py, tests/test_bloom_params_cpu.py
 static int show_batch(char *line)
 {
     unsigned long long n;
