@@ -1,6 +1,7 @@
 // rbf_api.hip -- C ABI (include/rbf.h) over the gfx950 kernels: the mask stage, the encode / decode chunks and the entry points, in
 // the order of the header.  One translation unit, split by #include:
 //   rbf_plan.h       which kernels serve a batch, and the frame tables they read (pure host code over rbf_geometry.h)
+//   rbf_mask_plan.h  the temporal chunks of the GOP mask kernels (pure host code; rbf_kernels_mask.h includes it)
 //   rbf_host.h       errors, context and scratch memory, timing, the shared hash table, shared argument checks and launches
 //   rbf_rice_host.h  host side of the sample codec
 // and the kernels it launches, one header per stage (rbf_kernels.h: the generic path):
@@ -94,47 +95,7 @@ static int prepare_ones_acc(rbf_ctx *ctx, uint32_t pairs)
     return RBF_OK;
 }
 
-// Temporal chunks of the fast mask kernel: enough waves to fill the chip (>= ~32 per CU) without re-reading much.  Returns the chunk
-// count (blockIdx.y).  *skip_in_table: the chunk table cuts the block at its keyframes, so the fast kernel needs no threshold trick.
-static uint32_t plan_mask_chunks(const Knobs &k, uint32_t nframes, uint64_t fast_segs, const uint8_t *skip, MaskChunks *mc, bool *skip_in_table)
-{
-    const uint32_t pairs = nframes - 1;
-    const uint32_t wanted = k.mask_chunks ? k.mask_chunks : (uint32_t)((6500 + fast_segs - 1) / fast_segs);   // 4 at 1080p (measured best)
-    *mc = MaskChunks{};
-    *skip_in_table = false;
-    uint32_t coded = pairs;
-    if (skip) { coded = 0; for (uint32_t i = 0; i < pairs; ++i) coded += skip[i] ? 0u : 1u; }
-    uint32_t chunks = std::max(1u, std::min(wanted, coded));
-    uint32_t ppc = std::max(1u, (coded + chunks - 1) / chunks);
-    if (skip && nframes < MASK_CHUNK_SKIP) {
-        uint32_t cnt = 0;
-        bool fits = true;
-        for (uint32_t a = 0; a < pairs && fits;) {
-            uint32_t b = a;
-            while (b < pairs && (skip[b] != 0) == (skip[a] != 0)) ++b;
-            const uint32_t len = b - a;
-            if (skip[a]) {
-                if (cnt >= MASK_MAX_CHUNKS) { fits = false; break; }
-                mc->first[cnt] = (uint16_t)a; mc->pairs[cnt] = (uint16_t)(len | MASK_CHUNK_SKIP); ++cnt;
-            } else {
-                const uint32_t c = (len + ppc - 1) / ppc, per = (len + c - 1) / c;     // this run in c chunks of about ppc pairs
-                for (uint32_t x = a; x < b; x += per) {
-                    if (cnt >= MASK_MAX_CHUNKS) { fits = false; break; }
-                    mc->first[cnt] = (uint16_t)x; mc->pairs[cnt] = (uint16_t)(b - x < per ? b - x : per); ++cnt;
-                }
-            }
-            a = b;
-        }
-        if (fits && cnt) { mc->count = cnt; *skip_in_table = true; return cnt; }
-        *mc = MaskChunks{};
-    }
-    if (skip) {         // (a block of more runs than the table holds) uniform chunks over everything, the skipped pairs through their thresholds
-        chunks = std::min(wanted, pairs);
-        ppc = (pairs + chunks - 1) / chunks;
-    }
-    mc->ppc = ppc;
-    return (pairs + ppc - 1) / ppc;
-}
+// (the temporal chunks of the fast mask kernel: plan_mask_chunks, rbf_mask_plan.h)
 
 // Per-pair thresholds travel as kernel arguments (captured at launch, so the caller's array is free as soon as we return) into a
 // device table.  A skipped pair gets INT32_MAX: `abs(diff) > thr` is then never true -- a zero row and a zero count.

@@ -3,6 +3,7 @@
 // chunk table and fused finish they take as arguments, and the two small kernels around them (k_store_thresholds, k_finish_ones).
 #pragma once
 #include "rbf_kernels.h"
+#include "rbf_mask_plan.h"
 
 namespace rbf {
 
@@ -173,15 +174,8 @@ struct MaskFinish {
     uint4 *clear_b; uint64_t quads_b;
 };
 
-// The temporal chunks of one launch (blockIdx.y).  count == 0: uniform chunks of `ppc` pairs over the whole block (one run).  Otherwise
-// chunk y reads frames first[y] .. first[y] + pairs[y] and writes the mask rows first[y] .. first[y] + pairs[y] - 1 -- so a block that
-// holds SEVERAL keyframe-delimited runs (rbf_encode_runs) is cut at the keyframes: no chunk reads across one, the pair in front of a
-// keyframe is never diffed.  pairs[y] & MASK_CHUNK_SKIP: those pairs are NOT coded; their rows are written as zeros, nothing is counted.
-constexpr uint32_t MASK_MAX_CHUNKS = 256, MASK_CHUNK_SKIP = 0x8000u;
-struct MaskChunks {
-    uint32_t count, ppc;
-    uint16_t first[MASK_MAX_CHUNKS], pairs[MASK_MAX_CHUNKS];
-};
+// The temporal chunks of one launch (blockIdx.y) -- MaskChunks, MASK_MAX_CHUNKS, MASK_CHUNK_SKIP -- and the host planner that fills them
+// live in rbf_mask_plan.h, which a plain host compiler takes.
 
 template <typename SAMPLE, int PIXEL_BYTES, bool NT = false, bool THR0 = false>
 __global__ __launch_bounds__(WG_THREADS) void k_residual_mask_gop(
