@@ -443,8 +443,11 @@ int rbf_pack_records(rbf_ctx *ctx, uint32_t nframes, uint64_t n, const rbf_filte
 
 /* ---- A6: decode  (BloomFilterCompressor.decompress loop, :286-307) ------------------------ */
 /* out mask bit i = witness[w++] if position i passes the filter, else 0.  filter_stride_bytes >= ceil(m/64)*8 for every m of the batch;
- * witness_stride_bytes: any multiple of 8 that holds every frame's witness bits (it may be smaller than ceil(n/64)*8); mask_stride_bytes
- * >= ceil(n/64)*8.  What is read and written in a row: rows of the Bloom entries, above. */
+ * witness_stride_bytes: any multiple of 8 (it may be smaller than ceil(n/64)*8); a caller who wants every witness bit read gives one
+ * that holds every frame's witness bits.  The filter decides how many positions pass, not the caller: where a frame passes more positions
+ * than its row holds bits -- a damaged or foreign filter --, a witness bit at or past witness_stride_bytes * 8 reads as 0, and nothing
+ * outside row f is read (tests/test_gpu_foreign_decode.py).  mask_stride_bytes >= ceil(n/64)*8.  What is read and written in a row: rows
+ * of the Bloom entries, above. */
 int rbf_bloom_decode_batch(rbf_ctx *ctx, const void *filters_dev, uint64_t filter_stride_bytes,
                            const void *witnesses_dev, uint64_t witness_stride_bytes,
                            uint64_t n, uint32_t nframes, const rbf_filter_params *params,

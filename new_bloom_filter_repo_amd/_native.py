@@ -329,7 +329,11 @@ def frame_geometry(a):
 
 
 def params_array(plist):
+    """The rbf_filter_params array of [(m, floor_k, T)].  ValueError for a value its field cannot hold: ctypes would wrap it without a word,
+    and the filter would be read under another geometry."""
     arr = (FilterParams * len(plist))()
     for i, (m, floor_k, thr) in enumerate(plist):
+        if not (0 <= int(m) < 1 << 32 and 0 <= int(floor_k) < 1 << 32 and 0 <= int(thr) < 1 << 64):
+            raise ValueError("frame %d: (m, floor_k, T) = (%d, %d, %d) does not fit rbf_filter_params" % (i, int(m), int(floor_k), int(thr)))
         arr[i].m, arr[i].floor_k, arr[i].threshold = int(m), int(floor_k), int(thr)
     return arr

@@ -41,17 +41,32 @@ def size(records):
 
 
 def parse(blob):
-    """[(type, record)] of a container."""
-    magic = blob[:4]
+    """[(type, record)] of a container.  A plain ValueError for bytes that are not a whole container: another magic, a header, a length
+    field or a body that is cut short, a count that the bytes cannot hold, a 'BFV2' record without its type byte, or bytes behind the
+    last record.  The message names the record."""
+    magic = bytes(blob[:4])
     if magic not in (b"BFVC", b"BFV2"):
         raise ValueError(f"Invalid file format: {magic}")
+    if len(blob) < 8:
+        raise ValueError("container of %d bytes is cut short in its header" % len(blob))
     (count,) = struct.unpack_from("<I", blob, 4)
+    if count > (len(blob) - 8) // 4:
+        raise ValueError("container declares %d records, its %d bytes cannot hold them" % (count, len(blob)))
     off, records = 8, []
-    for _ in range(count):
+    for i in range(count):
+        if off + 4 > len(blob):
+            raise ValueError("record %d of %d: the container ends in front of or inside its length field" % (i, count))
         (length,) = struct.unpack_from("<I", blob, off)
+        if off + 4 + length > len(blob):
+            raise ValueError("record %d of %d declares %d bytes, the container has %d left" % (i, count, length, len(blob) - off - 4))
         body = blob[off + 4: off + 4 + length]
         off += 4 + length
+        if magic == b"BFV2" and not length:
+            raise ValueError("record %d of %d is empty: a record starts with its type byte" % (i, count))
         records.append((KEY, body) if magic == b"BFVC" else (body[0], body[1:]))
+    if off != len(blob):
+        where = "record %d, the last of the %d the container declares" % (count - 1, count) if count else "the header of a container that declares no record"
+        raise ValueError("%d bytes behind %s" % (len(blob) - off, where))
     return records
 
 
@@ -113,7 +128,11 @@ def split_tables(records, frame_shape=None):
     if at[0] != len(frames):
         raise ValueError("the pan table is record %d, behind %d frame records: it stands directly behind the last frame record" % (at[0], len(frames)))
     pans = {}
-    for i, ox, oy in parse_pans(records[at[0]][1]):
+    try:
+        rows = parse_pans(records[at[0]][1])
+    except ValueError as e:
+        raise ValueError("record %d: %s" % (at[0], e)) from None
+    for i, ox, oy in rows:
         if i >= len(frames) or frames[i][0] not in INTERS:
             raise ValueError("pan table: record %d is no inter-frame record" % i)
         pans[i] = (ox, oy)
@@ -240,19 +259,22 @@ def split_trailer(records):
     if at[0] != len(records) - 1:
         raise ValueError("the digest trailer is record %d of %d: it may only be the last" % (at[0], len(records)))
     from .integrity import parse_trailer
-    digests = parse_trailer(records[-1][1])
+    try:
+        digests = parse_trailer(records[-1][1])
+    except ValueError as e:
+        raise ValueError("record %d: %s" % (at[0], e)) from None
     if len(digests) != len(records) - 1:
-        raise ValueError("the digest trailer covers %d frames, the container holds %d" % (len(digests), len(records) - 1))
+        raise ValueError("record %d: the digest trailer covers %d frames, the container holds %d" % (at[0], len(digests), len(records) - 1))
     return list(records[:-1]), digests
 
 
 def check_types(types):
-    """ValueError unless every type is known and the stream starts with a keyframe."""
-    for ty in types:
+    """ValueError, naming the record, unless every type is known and the stream starts with a keyframe."""
+    for i, ty in enumerate(types):
         if ty not in KEY_TYPES + INTERS:
-            raise ValueError(f"unknown record type {ty}")
+            raise ValueError(f"record {i}: unknown record type {ty}")
     if types and types[0] in INTERS:
-        raise ValueError("inter-frame without a preceding keyframe")
+        raise ValueError("record 0: inter-frame without a preceding keyframe")
 
 
 def inter_runs(types):

@@ -145,19 +145,35 @@ class FixedVideoCompressor:
         return finish
 
     def decompress_frame(self, blob):
+        """The frame of a keyframe record.  A plain ValueError for a record that is cut short or whose bytes do not inflate to the frame
+        its head declares."""
+        try:
+            return self._decompress_frame(blob)
+        except (struct.error, zlib.error, IndexError, UnicodeDecodeError, ZeroDivisionError, MemoryError) as e:
+            raise ValueError("damaged keyframe record: %s" % e) from None
+
+    def _decompress_frame(self, blob):
         h, w, item = struct.unpack_from("<III", blob, 0)
         (size,) = struct.unpack_from("<I", blob, 12)
         raw = zlib.decompress(blob[16:16 + size])
         dtype = {1: np.uint8, 2: np.uint16}.get(item, np.float32)
         gray = h * w * item
         if len(raw) > gray and len(raw) % gray == 0:
+            # at most four samples per pixel, as in a type-3 record: a damaged itemsize re-reads the same bytes as more samples of
+            # fewer bytes, which the frame digest -- taken over bytes -- cannot see
+            if len(raw) // gray > 4:
+                raise ValueError("keyframe record: %d samples per pixel" % (len(raw) // gray))
             frame = np.frombuffer(raw, dtype=dtype).reshape(h, w, len(raw) // gray)
         else:
             frame = np.frombuffer(raw, dtype=dtype).reshape(h, w)
         # trailer: '<B' has_yuv_info [| '<H' len, format | 3 x ('<I' len, zlib(plane), '<II' shape)]
         # (fixed_video_compressor.py:108-184: a frame written with yuv_info comes back as the wrapper)
         off = 16 + size
-        if off < len(blob) and blob[off] == 1:
+        if off >= len(blob) or blob[off] not in (0, 1):
+            raise ValueError("keyframe record: its has_yuv byte is %s" % ("missing" if off >= len(blob) else blob[off]))
+        if blob[off] == 0 and off + 1 != len(blob):
+            raise ValueError("keyframe record: %d bytes behind a frame without planes" % (len(blob) - off - 1))
+        if blob[off] == 1:
             off += 1
             (flen,) = struct.unpack_from("<H", blob, off)
             fmt = bytes(blob[off + 2:off + 2 + flen]).decode("utf-8")
@@ -172,6 +188,8 @@ class FixedVideoCompressor:
                 # the reference reads the planes as uint8 (fixed_video_compressor.py:155,163,171); planes of 16-bit frames keep the frame dtype
                 pdt = np.uint8 if len(pdata) == ph * pw else dtype
                 planes.append(np.frombuffer(pdata, dtype=pdt).reshape(ph, pw))
+            if off != len(blob):
+                raise ValueError("keyframe record: %d bytes behind its third plane" % (len(blob) - off))
             # the STORED planes come back in yuv_info, whatever their shape (a reference record may carry subsampled planes)
             out = YUVFrame.__new__(YUVFrame)
             out.data = frame
@@ -218,28 +236,38 @@ def build_record(wire_format, p, n, k, bitmap_bits, bitmap_packed, witness_bits,
 
 def parse_record(wire_format, compressed_data):
     """Fields of a wire record without decoding anything (:983-1012): dict with p, n, k, bitmap_bits,
-    witness_bits, bitmap (packed bytes), witness (packed bytes), values_z, value_count."""
+    witness_bits, bitmap (packed bytes), witness (packed bytes), values_z, value_count.  A plain ValueError for a record that is cut
+    short anywhere, whose bitmap or witness byte count is not ceil(bits / 8), or that is longer than its fields say."""
     mv = memoryview(compressed_data)
     off = 0
 
-    def take(fmt):
+    def take(fmt, what):
         nonlocal off
+        if off + struct.calcsize(fmt) > len(mv):
+            raise ValueError("truncated inter-frame record: its %d bytes end in front of or inside %s" % (len(mv), what))
         v = struct.unpack_from(fmt, mv, off)[0]
         off += struct.calcsize(fmt)
         return v
-    out = {"p": take("<f"), "n": take("<I"), "k": take("<f" if wire_format == "reference" else "<d"),
-           "bitmap_bits": take("<I"), "witness_bits": take("<I")}
-    size = take("<I")
-    out["bitmap"] = np.frombuffer(mv[off:off + size], dtype=np.uint8)
-    off += size
-    size = take("<I")
-    out["witness"] = np.frombuffer(mv[off:off + size], dtype=np.uint8)
-    off += size
-    vsize = take("<I")
-    out["value_count"] = take("<I")
+
+    def take_bytes(what, bits):
+        nonlocal off
+        size = take("<I", "the size of " + what)
+        if size != (bits + 7) // 8:
+            raise ValueError("inter-frame record: %d bytes of %s for %d bits" % (size, what, bits))
+        if off + size > len(mv):
+            raise ValueError("truncated inter-frame record: its %d bytes end inside %s" % (len(mv), what))
+        part = np.frombuffer(mv[off:off + size], dtype=np.uint8)
+        off += size
+        return part
+    out = {"p": take("<f", "p"), "n": take("<I", "n"), "k": take("<f" if wire_format == "reference" else "<d", "k"),
+           "bitmap_bits": take("<I", "bitmap_bits"), "witness_bits": take("<I", "witness_bits")}
+    out["bitmap"] = take_bytes("the bitmap", out["bitmap_bits"])
+    out["witness"] = take_bytes("the witness", out["witness_bits"])
+    vsize = take("<I", "the size of the values")
+    out["value_count"] = take("<I", "the value count")
+    if off + vsize != len(mv):
+        raise ValueError("inter-frame record: %d bytes of values declared, %d are there" % (vsize, len(mv) - off))
     out["values_z"] = bytes(mv[off:off + vsize])
-    if off + vsize > len(mv):
-        raise ValueError("truncated inter-frame record")
     return out
 
 

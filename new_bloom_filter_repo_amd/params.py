@@ -50,7 +50,18 @@ def activation_threshold(k_star):
     return floor_k, lo
 
 
+MAX_FLOOR_K = 64                               # include/rbf.h: rbf_filter_params.floor_k
+
+
 def filter_params(k_star, l):
-    """(m, floor_k, T) triple the C ABI takes for one filter."""
+    """(m, floor_k, T) triple the C ABI takes for one filter.  ValueError for what that ABI cannot take -- a k* that is not finite or
+    negative, a floor(k*) above 64, a filter length that is negative or does not fit 32 bits: the k* and the length of a record are
+    whatever its bytes say."""
+    if not math.isfinite(float(k_star)):
+        raise ValueError("k* = %r is not finite" % (k_star,))
+    if k_star < 0 or k_star >= MAX_FLOOR_K + 1:
+        raise ValueError("k* = %r: floor(k*) must be in 0..%d" % (k_star, MAX_FLOOR_K))
+    if not 0 <= int(l) < 1 << 32:
+        raise ValueError("filter length %d does not fit 32 bits" % int(l))
     floor_k, t = activation_threshold(k_star)
     return int(l), int(floor_k), int(t)

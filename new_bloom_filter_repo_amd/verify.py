@@ -199,7 +199,9 @@ def verify_container(path_or_bytes, **compressor_kwargs):
     frame mismatch: {"frames": frames decoded, "checked": frames compared with a stored digest, "bad": [indices of the frames whose digest
     does not match], "trailer": "ok" | "absent" (nothing to check against) | "damaged" (the trailer itself is not usable: the frames are
     decoded, none is checked)}.  compressor_kwargs go to the ImprovedVideoCompressor that decodes (chain_chunk_frames: its attribute of
-    that name).  What the records themselves make undecodable still raises."""
+    that name).  What the records themselves make undecodable still raises: a plain ValueError whose text names the record's index in
+    the stream -- never struct.error, IndexError, zlib.error, OverflowError, a numpy broadcasting error or an RbfError (decompress_video
+    has the contract) -- and no frame is reported that the records do not code."""
     from . import container
     from .video_compressor import ImprovedVideoCompressor
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):

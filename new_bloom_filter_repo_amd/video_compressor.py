@@ -184,6 +184,61 @@ def _close_timing(tm, t_all, busy):
     tm["gpu_busy_frac"] = tm["gpu_busy"] / tm["total"] if tm["total"] > 0 else 0.0
 
 
+def _inter_record(r, n, dtype, rice):
+    """The fields of an inter-frame record (type 2, or rice: type 4) behind a frame of n pixels and `dtype` samples, checked before any of
+    them reaches the device: the sample-width byte, n, the byte counts (parse_record), and
+      a coded record (witness_bits > 0)   a filter of at least one bit, and a k* and a length the C ABI takes (params.filter_params);
+      a passthrough one                    its bitmap IS the mask: bitmap_bits == n.  The pad bits behind bit n of its last byte are
+                                           cleared here -- the scatter walks every set bit of the mask's last word.
+    ValueError otherwise."""
+    if len(r) < 1 or r[0] not in (1, 2) or r[0] != np.dtype(dtype).itemsize:
+        raise ValueError("inter-frame record: sample-width byte %s behind a frame of %d-byte samples" % (r[0] if len(r) else "missing", np.dtype(dtype).itemsize))
+    d = parse_record("f64", r[1:])
+    if d["n"] != n:
+        raise ValueError("inter-frame record of %d pixels after a frame of %d" % (d["n"], n))
+    d["dtype"] = np.uint8 if r[0] == 1 else np.uint16
+    d["rice"] = bool(rice)
+    P.filter_params(d["k"], d["bitmap_bits"])                     # (k* and the length in range: of a passthrough record too)
+    if d["witness_bits"] > 0:
+        if d["bitmap_bits"] < 1:
+            raise ValueError("inter-frame record: %d witness bits and no filter" % d["witness_bits"])
+    else:
+        if d["bitmap_bits"] != n:
+            raise ValueError("inter-frame record without witness: its bitmap of %d bits is no mask of %d pixels" % (d["bitmap_bits"], n))
+        if n % 8:
+            mask = d["bitmap"].copy()
+            mask[-1] &= (0xFF << (8 - n % 8)) & 0xFF
+            d["bitmap"] = mask
+    if d["rice"]:
+        cnt, bits, size = stream_info(d["values_z"])
+        if (cnt, bits, size) != (d["value_count"], 8 * np.dtype(dtype).itemsize, len(d["values_z"])):
+            raise ValueError("type-4 record: its sample stream (%d %d-bit samples, %d bytes) does not match the record" % (cnt, bits, size))
+    return d
+
+
+_RECORD_ERRORS = (ValueError, struct.error, zlib.error, IndexError, OverflowError)
+
+
+@contextlib.contextmanager
+def _naming(first, last=None):
+    """Whatever the bytes of the records first .. last make a decoder raise comes out as a plain ValueError that names them by their
+    index in the stream (first None: the caller has no index; the error still comes out plain).  An IntegrityError speaks of a frame
+    already; an RbfError that is no refusal of an argument (RBF_EINVAL, RBF_ERANGE) is the device's and passes."""
+    from ._native import RBF_EINVAL, RBF_ERANGE, RbfError
+    try:
+        yield
+    except IntegrityError:
+        raise
+    except _RECORD_ERRORS + (RbfError,) as e:
+        if isinstance(e, RbfError) and e.code not in (RBF_EINVAL, RBF_ERANGE):
+            raise                                # the device's own trouble, not the record's
+        named = first is None or (type(e) is ValueError and str(e).startswith("record"))
+        if named and type(e) is ValueError:
+            raise
+        where = "" if named else ("record %d: " % first if last is None or last == first else "records %d..%d: " % (first, last))
+        raise ValueError("%s%s" % (where, e)) from None
+
+
 def _run_offsets(pan_table, lo, hi):
     """The cumulative pan offsets of the records lo .. hi-1 of a container, or None when none of them is rolled."""
     offs = [pan_table.get(i, (0, 0)) for i in range(lo, hi)]
@@ -916,6 +971,10 @@ class ImprovedVideoCompressor:
         where it is decoded; a type-1 keyframe by the host twin on the thread that inflated it.  The first frame, in stream order, whose
         digest is not the stored one raises IntegrityError (on_mismatch="collect": no exception, self.last_bad_frames lists them all --
         verify.verify_container).  self.last_integrity = {"frames", "checked", "device", "host"}.
+        Damage: a container whose bytes make a record undecodable raises a plain ValueError whose text names the record's index in
+        the stream (IntegrityError is a ValueError and names a frame) -- never struct.error, IndexError, zlib.error, OverflowError, a numpy
+        broadcasting error or an RbfError --, no frame comes back that the records do not code, and this object decodes a good container
+        bit for bit afterwards ("What a reader does with a damaged container").
         The keyframes are independent of everything else: they are inflated on the host threads while the inter-frame runs go through
         the GPU (type-3 keyframes are decoded on the lanes: by the run that hangs off them, or by a job of their own).  Every run hangs
         off its own keyframe, so the runs are independent too: they alternate over the lanes, each on its own host thread -- the inflate
@@ -931,10 +990,11 @@ class ImprovedVideoCompressor:
         busy = []
         key_pool = ThreadPoolExecutor(self.num_threads)
 
-        def key_job(rec):
-            frame = self.compressor.decompress_frame(rec)
+        def key_job(j, rec):
+            with _naming(j):
+                frame = self.compressor.decompress_frame(rec)
             return frame, frame_digest_host(frame_data(frame)) if log.checking else None
-        keys = {j: key_pool.submit(key_job, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
+        keys = {j: key_pool.submit(key_job, j, rec) for j, (ty, rec) in enumerate(records) if ty == KEY}
         runs = container.inter_runs(types)                                   # (index of the keyframe in front, first record, end)
         gkeys, decoded = {}, {}                                              # type-3 keyframes a run's job decoded; first record of a run -> its frames
 
@@ -943,11 +1003,12 @@ class ImprovedVideoCompressor:
             base = keys[k].result()[0] if types[k] == KEY else None          # (waits for the host's inflate without holding a lane)
             with take() as lane:
                 if base is None:
-                    base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
+                    with _naming(k):
+                        base = gkeys[k] = self._decode_key_rice(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
                 if lo is None:
                     return None
                 return self._decode_run(base, [rec for _, rec in records[lo:hi]], lane, key_pool, busy, types=types[lo:hi],
-                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, hi))
+                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, hi), first=lo)
         try:
             bases = {k for k, _, _ in runs}
             jobs = runs + [(j, None, None) for j, ty in enumerate(types) if ty in (KEY_RICE, KEY_NEAR) and j not in bases]     # lone type-3 keyframes: no run
@@ -965,14 +1026,15 @@ class ImprovedVideoCompressor:
                         if log.checking:
                             log.got[i] = (digest, "host")
                     else:
-                        frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=log.sink(i), near=types[i] == KEY_NEAR))
+                        with _naming(i):
+                            frames.append(gkeys[i] if i in gkeys else self._decode_key_rice(records[i][1], digest_out=log.sink(i), near=types[i] == KEY_NEAR))
                     i += 1
                     continue
                 if i in decoded:
                     frames += decoded[i]
                 else:
                     stabilised = []
-                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]], _run_offsets(pan_table, i, ends[i]), stabilised)
+                    frames += self._decode_frame_by_frame(frames[-1], records[i:ends[i]], _run_offsets(pan_table, i, ends[i]), stabilised, first=i)
                     log.host(i, stabilised)                                  # (the digests describe the frames the records code)
                 i = ends[i]
         finally:
@@ -1017,6 +1079,10 @@ class ImprovedVideoCompressor:
         decompress_video.
         A container with a trailer is checked for every frame that is REBUILT (verify_digests, on_mismatch, IntegrityError and
         last_bad_frames as in decompress_video, indices in clip numbering); the trailer's own digest and the pan table are checked whole.
+        Damage: a container whose bytes make a record undecodable raises a plain ValueError whose text names the record's index in
+        the stream (IntegrityError is a ValueError and names a frame) -- never struct.error, IndexError, zlib.error, OverflowError, a numpy
+        broadcasting error or an RbfError --, no view comes back of a frame that the records do not code, and this object decodes a good container
+        bit for bit afterwards ("What a reader does with a damaged container").
         self.last_read = {"records", "records_decoded", "frames_rebuilt", "frames_returned", "downloaded_bytes", "view_shape"}:
         downloaded_bytes is the sum over the frame downloads the call made -- the view blocks of the chains and of the decoded
         keyframes (masks and digests are not frames), counted where each download is made.  That holds on the batched route.  On the
@@ -1040,10 +1106,11 @@ class ImprovedVideoCompressor:
         fronts = {k for k, _, _, _ in runs}
         key_pool = ThreadPoolExecutor(self.num_threads)
 
-        def key_job(rec):
-            frame = self.compressor.decompress_frame(rec)
+        def key_job(j, rec):
+            with _naming(j):
+                frame = self.compressor.decompress_frame(rec)
             return frame, frame_digest_host(frame_data(frame)) if log.checking else None
-        inflated = {j: key_pool.submit(key_job, records[j][1]) for j in sorted(fronts | set(keys)) if types[j] == KEY}
+        inflated = {j: key_pool.submit(key_job, j, records[j][1]) for j in sorted(fronts | set(keys)) if types[j] == KEY}
         kviews, decoded = {}, {}                                             # wanted type-3 / type-7 keyframes -> their views; first record of a run -> its views
 
         def wrap(a, yuv):
@@ -1055,13 +1122,14 @@ class ImprovedVideoCompressor:
             with take() as lane:
                 yuv = isinstance(base, YUVFrame)
                 if base is None:
-                    base, yuv = self._decode_key_device(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
+                    with _naming(k):
+                        base, yuv = self._decode_key_device(records[k][1], lane, busy, digest_out=log.sink(k), near=types[k] == KEY_NEAR)
                     if k in keys:
                         kviews[k] = wrap(lane.sample_coder().fetch(base, view), yuv)
                 if lo is None:
                     return None
                 return self._decode_run(base, [rec for _, rec in records[lo:end]], lane, key_pool, busy, types=types[lo:end],
-                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, end), view=view.at(pos), yuv=yuv)
+                                        digests_out=log.sink(lo), offsets=_run_offsets(pan_table, lo, end), view=view.at(pos), yuv=yuv, first=lo)
         try:
             jobs = list(runs) + [(j, None, None, None) for j in keys if types[j] in (KEY_RICE, KEY_NEAR) and j not in fronts]     # lone type-3 keyframes: no run
             if self.gop_batching and jobs:
@@ -1073,14 +1141,15 @@ class ImprovedVideoCompressor:
                     if types[k] == KEY:
                         base = inflated[k].result()[0]
                     else:
-                        base = self._decode_key_rice(records[k][1], digest_out=log.sink(k), near=types[k] == KEY_NEAR)
+                        with _naming(k):
+                            base = self._decode_key_rice(records[k][1], digest_out=log.sink(k), near=types[k] == KEY_NEAR)
                         view.downloads.append(base.nbytes)
                         if k in keys:
                             kviews[k] = wrap(view_host(frame_data(base), roi, scale), isinstance(base, YUVFrame))
                     if lo is None:
                         continue
                     stabilised = []
-                    whole = self._decode_frame_by_frame(base, records[lo:end], _run_offsets(pan_table, lo, end), stabilised)
+                    whole = self._decode_frame_by_frame(base, records[lo:end], _run_offsets(pan_table, lo, end), stabilised, first=lo)
                     log.host(lo, stabilised)                                 # (the digests describe the frames the records code)
                     view.downloads.append(sum(f.nbytes for (ty, _), f in zip(records[lo:end], whole) if ty == INTER_RICE))
                     decoded[lo] = [wrap(view_host(frame_data(whole[p]), roi, scale), isinstance(base, YUVFrame)) for p in pos]
@@ -1106,24 +1175,34 @@ class ImprovedVideoCompressor:
             raise IntegrityError(i, log.expected[i], log.got[i][0], key_record=max(j for j in range(i + 1) if types[j] in KEY_TYPES))
         return frames
 
-    def _decode_frame_by_frame(self, base, records, offsets=None, stabilised_out=None):
+    def _decode_frame_by_frame(self, base, records, offsets=None, stabilised_out=None, first=None):
         """The frames of a run of inter-frame records after `base`, one record at a time (gop_batching=False).  offsets: the records'
         cumulative pan offsets (ox, oy), or None -- the records code the STABILISED frames, each is rolled back on the host (np.roll)
         after the next record has been applied to it; stabilised_out: a list that receives the frames as the records code them."""
         frames = []
-        for ty, r in records:
+        for j, (ty, r) in enumerate(records):
+            at = None if first is None else first + j
             if ty == INTER_RICE:
-                frames += self._decode_run(base, [r], types=[INTER_RICE])
+                frames += self._decode_run(base, [r], types=[INTER_RICE], first=at)
             else:
-                dtype = np.uint8 if r[0] == 1 else np.uint16
-                mask, values = self.inter._decompress_frame_differences(r[1:], base.shape, dtype=dtype)
-                frames.append(self.inter._apply_frame_diff(base, mask, values))
+                with _naming(at):
+                    arr = frame_data(base)
+                    n = arr.shape[0] * arr.shape[1]
+                    d = self._parse_run(arr, [r], [ty])[0]                       # the checks of the batched route, before anything is decoded
+                    values = np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])
+                    if len(values) != d["value_count"]:
+                        raise ValueError("inter-frame record: %d values declared, %d inflated" % (d["value_count"], len(values)))
+                    if d["witness_bits"] > 0:                                    # (the witness as the batched route takes it: its whole bytes)
+                        mask = self.inter.bloom_compressor.decompress(np.unpackbits(d["bitmap"])[:d["bitmap_bits"]], np.unpackbits(d["witness"]), n, d["k"])
+                    else:
+                        mask = np.unpackbits(d["bitmap"])[:n]
+                    frames.append(self.inter._apply_frame_diff(base, np.asarray(mask, dtype=np.uint8).reshape(arr.shape[:2]), values))
             base = frames[-1]
         if stabilised_out is not None:
             stabilised_out += frames
         if offsets is None:
             return frames
-        container.check_pans({i: o for i, o in enumerate(offsets)}, frame_data(base).shape)
+        container.check_pans({(i if first is None else first + i): o for i, o in enumerate(offsets)}, frame_data(base).shape)
         out = []
         for f, (ox, oy) in zip(frames, offsets):
             if (ox, oy) != (0, 0):
@@ -1133,40 +1212,34 @@ class ImprovedVideoCompressor:
         return out
 
     @staticmethod
-    def _parse_run(base_arr, recs, types):
+    def _parse_run(base_arr, recs, types, first=None):
         """The records of a run after the frame `base_arr`, parsed ("f64" wire format) and checked against it; each dict also carries
-        `dtype` (of its values) and `rice` (a type-4 record: its value field is a sample stream)."""
+        `dtype` (of its values) and `rice` (a type-4 record: its value field is a sample stream).  first: the index of recs[0] in the stream,
+        which a ValueError then names (_inter_record has the checks)."""
         n = base_arr.shape[0] * base_arr.shape[1]
         parsed = []
-        for ty, r in zip(types, recs):
-            d = parse_record("f64", r[1:])
-            if d["n"] != n:
-                raise ValueError("inter-frame record of %d pixels after a frame of %d" % (d["n"], n))
-            d["dtype"] = np.uint8 if r[0] == 1 else np.uint16
-            d["rice"] = ty == INTER_RICE
-            if d["rice"]:
-                cnt, bits, size = stream_info(d["values_z"])
-                if (cnt, bits, size) != (d["value_count"], 8 * base_arr.dtype.itemsize, len(d["values_z"])) or d["dtype"] != base_arr.dtype:
-                    raise ValueError("type-4 record: its sample stream (%d %d-bit samples, %d bytes) does not match the record" % (cnt, bits, size))
-            parsed.append(d)
+        for j, (ty, r) in enumerate(zip(types, recs)):
+            with _naming(None if first is None else first + j):
+                parsed.append(_inter_record(r, n, base_arr.dtype, ty == INTER_RICE))
         return parsed
 
     @staticmethod
-    def _fit_values(parsed, masks, vals, n, ch):
+    def _fit_values(parsed, masks, vals, n, ch, first=None):
         """Every record's value count against its decoded mask (in place): a type-4 stream that does not fit its mask is an error, so is a
         single-channel type-2 record; a colour frame with a mismatching value count is left untouched."""
+        name = lambda i: "" if first is None else "record %d: " % (first + i)
         for i, (m, v) in enumerate(zip(masks, vals)):
             ones = _popcount(np.asarray(m, dtype=np.uint8)[:(n + 7) // 8])
             if parsed[i]["rice"]:                # no reference behaviour to keep: a stream that does not fit its mask is an error
                 if parsed[i]["value_count"] != ones * ch:
-                    raise ValueError("type-4 record: %d residuals for a mask of %d pixels" % (parsed[i]["value_count"], ones))
+                    raise ValueError("%stype-4 record: %d residuals for a mask of %d pixels" % (name(i), parsed[i]["value_count"], ones))
                 continue
             if len(v) != ones * ch:              # same rule as _apply_frame_diff (:886-903)
                 if ch == 1:
-                    raise ValueError("changed_values does not match the mask")
+                    raise ValueError("%schanged_values does not match the mask" % name(i))
                 masks[i], vals[i] = np.zeros((n + 7) // 8, np.uint8), v[:0]      # color: frame left untouched
 
-    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None, offsets=None, view=None, yuv=None):
+    def _decode_run(self, base, recs, lane=None, pool=None, busy=None, types=None, digests_out=None, offsets=None, view=None, yuv=None, first=None):
         """A run of inter-frame records after `base`: the masks of all Bloom-coded frames are decoded in
         ONE rbf_bloom_decode_batch, the changed values are inflated in threads, and the frames are
         rebuilt in sequence on the device (engine.apply_chain; type-4 records: SampleCoder.apply_chain).  lane: the context to use
@@ -1191,10 +1264,15 @@ class ImprovedVideoCompressor:
         yuv = isinstance(base, YUVFrame) if yuv is None else yuv
         H, W, ch, _ = frame_geometry(base_arr)
         n = H * W
-        parsed = self._parse_run(base_arr, recs, types)
+        at = lambda j: None if first is None else first + j                  # a record's index in the stream, for the errors
+        parsed = self._parse_run(base_arr, recs, types, first)
         if view is not None and any(d["rice"] != parsed[0]["rice"] for d in parsed):
             raise ValueError("a run that mixes record types 2 and 4 cannot be read in part: decompress_video reads it")
-        inflate = lambda d: np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])[:d["value_count"]]
+        def inflate(d):
+            v = np.frombuffer(zlib.decompress(d["values_z"]), dtype=d["dtype"])
+            if len(v) != d["value_count"]:
+                raise ValueError("inter-frame record: %d values declared, %d inflated" % (d["value_count"], len(v)))
+            return v
         own_pool = None
         if pool is None:
             pool = own_pool = ThreadPoolExecutor(self.num_threads)
@@ -1203,23 +1281,27 @@ class ImprovedVideoCompressor:
         coded = [d for d in parsed if d["witness_bits"] > 0]
         if coded:
             plist = [P.filter_params(d["k"], d["bitmap_bits"]) for d in coded]
-            masks = lane.decode_engine().decode(n, plist, [d["bitmap"] for d in coded], [d["witness"] for d in coded])
+            with _naming(at(0), at(len(recs) - 1)):
+                masks = lane.decode_engine().decode(n, plist, [d["bitmap"] for d in coded], [d["witness"] for d in coded])
             for d, m in zip(coded, masks):
                 d["mask"] = m
         t2 = time.perf_counter()
-        vals = [d["values_z"] if j is None else j.result() for j, d in zip(val_jobs, parsed)]
+        vals = []
+        for i, (j, d) in enumerate(zip(val_jobs, parsed)):
+            with _naming(at(i)):
+                vals.append(d["values_z"] if j is None else j.result())
         if own_pool is not None:
             own_pool.shutdown()
         t3 = time.perf_counter()
         masks = [d["mask"] if "mask" in d else d["bitmap"][:(n + 7) // 8] for d in parsed]
-        self._fit_values(parsed, masks, vals, n, ch)
+        self._fit_values(parsed, masks, vals, n, ch, first)
         t4 = time.perf_counter()
         out, prev, i = [], base_arr, 0
         hook = None if digests_out is None else (lambda ptr, fbytes, cnt: digests_out.extend(int(x) for x in lane.digests(ptr, fbytes, cnt, fbytes)))
         chunk = self.chain_chunk_frames
         fbytes, pixel_bytes = base_arr.nbytes, base_arr.nbytes // n
         if offsets is not None:
-            container.check_pans({k: o for k, o in enumerate(offsets)}, base_arr.shape)
+            container.check_pans({(k if first is None else first + k): o for k, o in enumerate(offsets)}, base_arr.shape)
 
         def unroll(fb, c0, cnt):
             """rebuild_chain's before_download hook: it runs inside the apply_chain calls below, where `i` is the record of the run the
@@ -1237,10 +1319,11 @@ class ImprovedVideoCompressor:
             j = i
             while j < len(parsed) and parsed[j]["rice"] == parsed[i]["rice"]:
                 j += 1
-            if parsed[i]["rice"]:
-                part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
-            else:
-                part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
+            with _naming(at(i), at(j - 1)):              # (a sample stream whose codes do not end inside its words is found on the device: RBF_EINVAL)
+                if parsed[i]["rice"]:
+                    part = lane.sample_coder().apply_chain(prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
+                else:
+                    part = apply_chain(lane.ctx, prev, masks[i:j], vals[i:j], chunk_frames=chunk, on_rebuilt=hook, before_download=before, view=view)
             out += part
             prev, i = part[-1] if view is None else None, j               # (a viewed run is one stretch: nothing continues it)
             if offsets is not None and i < len(parsed) and offsets[i - 1] != (0, 0):      # the next stretch continues the stabilised frame
